@@ -10,8 +10,16 @@ on synthetic CIFAR-shaped data, with the FedAvg parameter-subset all-reduce
 timed region — a HIGHER communication cadence than the reference's
 once-per-epoch (~49 steps at K=8), so comm cost is over- not under-counted.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     # N>1 is launched by the driver via torch.distributed.run (one rank/GPU)
+
+A plain run does only what the headline figure needs: setup, warmup, the
+K timed steps, the optional output dump, the result line.  --full is the
+switch for any extra measurement (none exist yet, so it changes nothing).
+--dump-outputs DIR writes what the last timed step computed (loss, logits,
+the updated parameters and BN buffers) as float32 DIR/<name>.npy; seeds are
+fixed, so two builds run with the same arguments see identical inputs and
+can be compared output for output.
 
 Prints ONE JSON line from rank 0: value = whole-job images/sec over all N
 GPUs (weak scaling: per-GPU batch fixed at 128).
@@ -31,6 +39,29 @@ AGG_EVERY = 12
 BATCH = 128
 
 
+def dump_outputs(out_dir, net, last):
+    """What a caller of the timed step receives after the LAST timed step:
+    its loss and logits, and the model state the step left behind (all
+    parameters flattened in net.parameters() order, all floating-point
+    buffers in net.buffers() order).  float32 .npy, ~45 MB for ResNet18."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def flat32(ts):
+        ts = [t.detach().float().reshape(-1) for t in ts]
+        return torch.cat(ts).cpu().numpy() if ts else np.zeros(0, np.float32)
+
+    arrays = {
+        "loss": last["loss"].detach().float().reshape(1).cpu().numpy(),
+        "logits": last["logits"].detach().float().cpu().numpy(),
+        "params": flat32(net.parameters()),
+        "buffers": flat32(b for b in net.buffers() if b.is_floating_point()),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2**20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -46,6 +77,14 @@ def main():
                          "on another with the run order reversed) — the "
                          "apparent gain tracks thermal run order, not the "
                          "graph; default off, kept for A/B")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write the last step's "
+                         "results (loss, logits, updated parameters, BN "
+                         "buffers) as float32 DIR/<name>.npy (~45 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extended measurements; off by "
+                         "default.  The benchmark has none beyond the "
+                         "headline today, so this is currently a no-op")
     args = ap.parse_args()
 
     if not args.native:
@@ -121,6 +160,7 @@ def main():
         flat_ops.unpack(vec, bp)
 
     step_i = 0
+    last = {}   # logits / loss of the most recent step (for --dump-outputs)
 
     def eager_step(x, y, keep_grad_buffers=False):
         # set_to_none=True matters eagerly: with persistent grad buffers
@@ -129,9 +169,11 @@ def main():
         # buffers kept
         opt.zero_grad(set_to_none=not keep_grad_buffers)
         with autocast():
-            loss = L.cross_entropy(net(x), y)
+            out = net(x)
+            loss = L.cross_entropy(out, y)
         loss.backward()
         opt.step()
+        last["logits"], last["loss"] = out, loss
 
     # ---- hipGraph capture of the local step (MI355X: the inner loop is
     # launch-bound; one graph replay replaces ~380 host enqueues).  The
@@ -236,6 +278,9 @@ def main():
                 "native_kernels": bool(args.native and use_cuda),
             },
         }))
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, last)
 
     if distributed:
         dist.destroy_process_group()

@@ -293,3 +293,34 @@ def test_cpc_driver_cpu_end_to_end(tmp_path):
         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0, r.stderr[-800:]
     assert "dual (N=" in r.stdout     # reference-format FedAvg residual
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: one JSON result line whose steps/ms_per_step
+    reflect --steps, and float32 .npy files of the last timed step (loss,
+    logits, parameters, BN buffers) under the 64 MB cap; --full is accepted."""
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
+    r = subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1",
+         "--steps", "3", "--warmup", "1", "--batch", "16", "--full",
+         "--dump-outputs", str(dump)],
+        capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-800:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "images_per_sec" and rec["steps"] == 3
+    assert rec["ms_per_step"] > 0
+    assert abs(rec["value"] * rec["ms_per_step"] / 1000.0 - 16) < 0.05 * 16
+    arrs = {n: np.load(dump / (n + ".npy"))
+            for n in ("loss", "logits", "params", "buffers")}
+    assert sorted(os.listdir(dump)) == sorted(n + ".npy" for n in arrs)
+    assert all(a.dtype == np.float32 for a in arrs.values())
+    assert all(np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+    assert arrs["logits"].shape == (16, 10) and arrs["loss"].shape == (1,)
+    assert arrs["params"].size == 11173962   # ResNet18, 10 classes
