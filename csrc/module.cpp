@@ -27,6 +27,21 @@ void fedkit_cast_f32_to_bf16(std::vector<at::Tensor> srcs,
 void fedkit_cast_bf16_to_f32(std::vector<at::Tensor> srcs,
                              std::vector<at::Tensor> dsts);
 
+at::Tensor fedkit_penalty_fwd(std::vector<at::Tensor> params,
+                              c10::optional<at::Tensor> z,
+                              c10::optional<at::Tensor> y, double rho,
+                              double lambda1, double lambda2);
+at::Tensor fedkit_penalty_bwd(std::vector<at::Tensor> params,
+                              c10::optional<at::Tensor> z,
+                              c10::optional<at::Tensor> y, double rho,
+                              double lambda1, double lambda2,
+                              const at::Tensor& grad_out);
+at::Tensor fedkit_admm_dual_update(at::Tensor y, const at::Tensor& x,
+                                   const at::Tensor& z, double rho);
+at::Tensor fedkit_bb_stats(const at::Tensor& y, const at::Tensor& yhat0,
+                           const at::Tensor& x, const at::Tensor& z,
+                           const at::Tensor& x0);
+
 std::vector<at::Tensor> fedkit_cross_entropy_fwd(const at::Tensor& logits,
                                                  const at::Tensor& labels);
 at::Tensor fedkit_cross_entropy_bwd(const at::Tensor& logits,
@@ -139,6 +154,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "batched fp32->bf16 tensor casts (one kernel for <=48 tensors)");
   m.def("cast_bf16_to_f32", &fedkit_cast_bf16_to_f32,
         "batched bf16->fp32 tensor casts");
+  m.def("penalty_fwd", &fedkit_penalty_fwd,
+        "fused consensus penalty + L1/L2 regulariser over a parameter list "
+        "read in place -> device fp32 scalar (deterministic)",
+        py::arg("params"), py::arg("z"), py::arg("y"), py::arg("rho"),
+        py::arg("lambda1"), py::arg("lambda2"));
+  m.def("penalty_bwd", &fedkit_penalty_bwd,
+        "closed-form penalty gradient -> flat fp32 [N] in physical order",
+        py::arg("params"), py::arg("z"), py::arg("y"), py::arg("rho"),
+        py::arg("lambda1"), py::arg("lambda2"), py::arg("grad_out"));
+  m.def("admm_dual_update", &fedkit_admm_dual_update,
+        "y += rho (x - z) in place; returns device sum (rho (x - z))^2");
+  m.def("bb_stats", &fedkit_bb_stats,
+        "six Barzilai-Borwein inner products in one pass -> device fp32 [6]");
   m.def("cross_entropy_fwd", &fedkit_cross_entropy_fwd,
         "fused log-softmax + NLL (mean): returns (loss, lse)");
   m.def("cross_entropy_bwd", &fedkit_cross_entropy_bwd, "CE backward");

@@ -32,6 +32,8 @@ from typing import Dict, Optional
 
 import torch
 
+from ..ops import consensus, native_enabled
+
 from typing import TYPE_CHECKING
 if TYPE_CHECKING:  # avoid the algos <-> parallel import cycle at runtime
     from ..parallel.comm import Communicator
@@ -62,6 +64,11 @@ class Strategy:
 
     def penalty(self, state: dict, ck: int, xvec: torch.Tensor):
         """Extra (differentiable) loss term for client ck's closure."""
+        return None
+
+    def penalty_args(self, state: dict, ck: int) -> Optional[dict]:
+        """The same term as `penalty`, as keyword arguments {z, y, rho} for
+        the fused fedkit.ops.consensus.penalty; None = no penalty term."""
         return None
 
     def aggregate(self, comm: Communicator, state: dict,
@@ -156,6 +163,12 @@ class FedProx(Strategy):
         rho = self._rho(state.get("block_idx", 0), ck)
         return 0.5 * rho * (torch.norm(xdelta, 2) ** 2)
 
+    def penalty_args(self, state, ck):
+        if state.get("round", 0) < self.warmup_rounds:
+            return None
+        return {"z": state["z"], "y": None,
+                "rho": self._rho(state.get("block_idx", 0), ck)}
+
     def aggregate_start(self, comm, state, x):
         return comm.sum_across_clients_async(
             {k: v.clone() for k, v in x.items()})
@@ -223,6 +236,11 @@ class ConsensusADMM(Strategy):
         return torch.dot(state["y"][ck], xdelta) \
             + 0.5 * state["rho"] * (torch.norm(xdelta, 2) ** 2)
 
+    def penalty_args(self, state, ck):
+        if state.get("round", 0) < self.warmup_rounds:
+            return None
+        return {"z": state["z"], "y": state["y"][ck], "rho": state["rho"]}
+
     def _bb_update(self, comm, state, x, round_idx):
         """Replicated deterministic BB rho chain (consensus_multi.py:241-278)."""
         bb = self.bb
@@ -236,6 +254,12 @@ class ConsensusADMM(Strategy):
         # per-client scalars: a = y - yhat0, b = x - z, dx = x - x0
         per_client = {}
         for ck in comm.my_clients:
+            if native_enabled(z):
+                # one fused pass over the five vectors, one host sync
+                per_client[ck] = consensus.bb_stats(
+                    state["y"][ck], state["yhat0"][ck], x[ck], z,
+                    state["x0"][ck]).tolist()
+                continue
             a = state["y"][ck] - state["yhat0"][ck]
             b = x[ck] - z
             dx = x[ck] - state["x0"][ck]
@@ -285,6 +309,12 @@ class ConsensusADMM(Strategy):
         # dual variable + primal residual (consensus_multi.py:291-296)
         per_client = {}
         for ck in x:
+            if native_enabled(znew):
+                # y += rho (x - znew) and ||rho (x - znew)||^2 in one pass
+                sq = consensus.admm_dual_update(state["y"][ck], x[ck], znew,
+                                                rho)
+                per_client[ck] = [math.sqrt(sq.item())]
+                continue
             ydelta = rho * (x[ck] - znew)
             per_client[ck] = [torch.norm(ydelta).item()]
             state["y"][ck].add_(ydelta)

@@ -10,6 +10,8 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
   bn_fwd / bn_bwd                NHWC BatchNorm with fused ELU epilogue
   cross_entropy_fwd/bwd          fused log-softmax + NLL
   add_elu_fwd / add_elu_bwd      fused residual-add + ELU
+  penalty_fwd / penalty_bwd      fused FedProx/ADMM penalty + L1/L2 regulariser
+  admm_dual_update / bb_stats    fused ADMM y-update and BB inner products
 
 Dispatch policy (this is the "native code is THE path that runs" rule):
   * on a ROCm GPU the HIP kernels are used; if the extension is missing the
@@ -103,7 +105,7 @@ def native_enabled(t: torch.Tensor) -> bool:
     return _NATIVE_ENV and t.is_cuda
 
 
-from . import elu, flat, losses          # noqa: E402,F401
+from . import consensus, elu, flat, losses  # noqa: E402,F401
 from .conv import (FedConv2d, FedConvGeneric,  # noqa: E402
                    FedConvTranspose2d)
 from .pool import FedMaxPool2d, max_pool2d, avg_pool2d  # noqa: E402
@@ -112,7 +114,7 @@ from .linear import FedLinear            # noqa: E402
 
 __all__ = [
     "ext", "has_ext", "require_ext", "native_enabled",
-    "elu", "flat", "losses", "FedConv2d", "FedConvGeneric",
+    "consensus", "elu", "flat", "losses", "FedConv2d", "FedConvGeneric",
     "FedMaxPool2d", "max_pool2d", "avg_pool2d",
     "FedConvTranspose2d", "FedBatchNorm2d", "FedLinear",
 ]

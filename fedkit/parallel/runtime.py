@@ -41,6 +41,8 @@ from ..algos import BBConfig, ConsensusADMM, FedAvg, FedProx, NoConsensus, Strat
 from ..data import make_client_datasets
 from ..models import MODEL_FACTORIES
 from ..optim import FusedAdam, LBFGSNew
+from ..ops import native_enabled
+from ..ops import consensus as consensus_ops
 from ..ops import losses as loss_ops
 from ..utils import (flat_trainable, freeze_all_layers, get_trainable_values,
                      init_weights, number_of_blocks, put_trainable_values,
@@ -101,6 +103,9 @@ class FedConfig:
                                        # failure-recovery minimum)
     l2_all_blocks: bool = False        # VAE-CL: L2 reg on every block
                                        # (federated_vae_cl.py:230)
+    fused_penalty: bool = True         # GPU: FedProx/ADMM penalty + L1/L2
+                                       # regulariser as one fused HIP op
+                                       # (False = the torch expression)
 
     def model_name(self) -> str:
         if self.model:
@@ -240,6 +245,16 @@ class FederatedJob:
         net = self.nets[ck]
         running_loss = 0.0
         lin_ids = net.linear_layer_ids() if hasattr(net, "linear_layer_ids") else []
+        # fused penalty path: one HIP reduction over the parameter tensors
+        # in place (+ one closed-form gradient kernel) instead of the
+        # cat / penalty / norm chain below and its autograd replay
+        tparams = trainable_params(net)
+        fused = (cfg.fused_penalty and len(tparams) > 0
+                 and native_enabled(tparams[0])
+                 and all(p.dtype == torch.float32 and not p.is_sparse
+                         and (p.is_contiguous() or p.is_contiguous(
+                             memory_format=torch.channels_last))
+                         for p in tparams))
         for i, (inputs, labels) in enumerate(self.train_loaders[ck]):
             if cfg.max_steps_per_epoch and i >= cfg.max_steps_per_epoch:
                 break
@@ -251,7 +266,15 @@ class FederatedJob:
                     loss = self.loss_fn(net, inputs, labels)
                 loss = loss.float()
                 reg_on = (ci in lin_ids) or cfg.l2_all_blocks
-                if self.strategy.uses_penalty or reg_on:
+                if fused:
+                    pargs = self.strategy.penalty_args(self._state, ck)
+                    if pargs is not None or reg_on:
+                        loss = loss + consensus_ops.penalty(
+                            tparams,
+                            lambda1=cfg.lambda1 if reg_on else 0.0,
+                            lambda2=cfg.lambda2 if reg_on else 0.0,
+                            **(pargs or {}))
+                elif self.strategy.uses_penalty or reg_on:
                     # PHYSICAL element order so the FedProx/ADMM penalty's
                     # (x - z) pairs elements the way the packed z was built
                     # (channels_last weights reorder under reshape(-1))

@@ -18,6 +18,7 @@ SOURCES = [
     "csrc/module.cpp",
     "csrc/elementwise.hip",
     "csrc/flat_ops.hip",
+    "csrc/consensus.hip",
     "csrc/loss.hip",
     "csrc/losses_extra.hip",
     "csrc/linear.hip",
