@@ -17,9 +17,20 @@
 // ~190 us flat).  The separate wave-per-column colsum launch is ~6 us and
 // is the latency floor here.
 // All statistics fp32 regardless of activation dtype (bf16 data paths keep
-// fp32 BN stats — SURVEY.md §7 hard part 4).  C must divide 256 or be a
-// multiple of 256 (ResNet: 64/128/256/512) so each thread owns ONE channel
-// across its grid-stride walk; asserted on the host side.
+// fp32 BN stats — SURVEY.md §7 hard part 4).  With VEC = 16 B / sizeof(T)
+// channels per lane (4 for fp32, 8 for bf16) the reduction kernels need
+// C % VEC == 0 and (C / VEC) | 256, i.e. C = VEC * 2^k with k = 0..8: fp32
+// C in {4, 8, .., 1024}, bf16 C in {8, 16, .., 2048} (ResNet:
+// 64/128/256/512).  Then each thread owns ONE channel group across its
+// grid-stride walk.  C = 24, 96, or 2048 in fp32 are REJECTED; the host
+// side checks this before anything is launched.  (Eval mode and the
+// conv-epilogue statistics path run no reduction and need only C % VEC.)
+// The variance is the one-pass form var = E[x^2] - mean^2 accumulated in
+// fp32, which loses about (1 + r^2) units of roundoff for a channel with
+// r = |mean| / std.  It is tested to hold save_invstd within
+// d * 2^-24 * (1 + r^2) (d = addition depth of the reduction, 25 at the
+// tested shape) up to r = 32, where that bound is still below one bf16
+// half-ulp; channels far beyond that ratio would need a shifted sum.
 
 #include "fedkit_common.h"
 
@@ -90,6 +101,17 @@ __global__ void bn_partials_kernel(const T* __restrict__ x, long long M,
   }
 }
 
+// biased variance from E[x^2] and the mean.  One value per channel
+// (count == 1) has variance 0 by definition; computed, it would be the
+// rounding residue of x^2 (the compiler contracts the expression into
+// fma(-mean, mean, E[x^2]), which sees the exact square), and that
+// residue, ~6e-8 * x^2, against eps = 1e-5 put save_invstd off by 3e-3.
+// For count > 1 the arithmetic is unchanged.
+__device__ __forceinline__ float biased_var(float ex2, float mean,
+                                            long long count) {
+  return count > 1 ? fmaxf(ex2 - mean * mean, 0.f) : 0.f;
+}
+
 // stage 2: sum the per-block partial rows, then mean/invstd + running update
 __global__ void bn_finalize_kernel(const float* __restrict__ part, int nb,
                                    int C, long long count, float eps,
@@ -108,7 +130,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ part, int nb,
       sq += part[(long long)b * 2 * C + C + c];
     }
     mean = s / count;
-    var = fmaxf(sq / count - mean * mean, 0.f);  // biased
+    var = biased_var(sq / count, mean, count);
     if (track) {
       float unbiased = count > 1 ? var * count / (count - 1) : var;
       running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
@@ -163,7 +185,7 @@ __global__ void bn_colsum_finalize_kernel(
   }
   if (lane == 0) {
     float mean = s / count;
-    float var = fmaxf(sq / count - mean * mean, 0.f);  // biased
+    float var = biased_var(sq / count, mean, count);
     if (track) {
       float unbiased = count > 1 ? var * count / (count - 1) : var;
       running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
@@ -200,7 +222,7 @@ __global__ void bn_conv_colsum_finalize_kernel(
   }
   if (lane == 0) {
     float mean = s / count;
-    float var = fmaxf(sq / count - mean * mean, 0.f);  // biased
+    float var = biased_var(sq / count, mean, count);
     if (track) {
       float unbiased = count > 1 ? var * count / (count - 1) : var;
       running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
@@ -444,6 +466,40 @@ std::vector<at::Tensor> fedkit_bn_fwd(const at::Tensor& x,
   check_nhwc(x);
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   long long M = (long long)N * H * W;
+  // every argument is validated BEFORE the first launch: a rejected call
+  // must leave running_mean / running_var untouched
+  TORCH_CHECK(x.scalar_type() == at::kFloat ||
+              x.scalar_type() == at::kBFloat16, "bn expects fp32 or bf16");
+  const int vec = 16 / (int)x.element_size();
+  TORCH_CHECK(C % vec == 0, "bn needs C % ", vec, " == 0, got C=", C);
+  const bool from_conv = training && conv_part.has_value();
+  TORCH_CHECK(!training || from_conv || 256 % (C / vec) == 0,
+              "bn kernel needs C % ", vec, " == 0 and (C/", vec,
+              ") | 256, got C=", C);
+  TORCH_CHECK(gamma.scalar_type() == at::kFloat, "bn gamma must be fp32");
+  TORCH_CHECK(pad_out >= 0 && res_pad >= 0, "bn pads must be >= 0");
+  if (from_conv) {
+    auto& cp = *conv_part;
+    TORCH_CHECK(cp.scalar_type() == at::kFloat && cp.dim() == 4 &&
+                cp.size(0) * 64 == C && cp.size(2) == 2 && cp.size(3) == 64,
+                "bad conv_part shape for C=", C);
+    TORCH_CHECK(cp.device() == x.device(),
+                "conv_part must live on the input's device");
+    TORCH_CHECK(cp.is_contiguous(), "conv_part must be contiguous");
+    // the producing conv launches 64- or 128-row tiles, nothing else
+    TORCH_CHECK(cp.size(1) == (M + 63) / 64 || cp.size(1) == (M + 127) / 128,
+                "conv_part has ", cp.size(1), " tile rows, impossible for M=",
+                M);
+  }
+  if (residual.has_value()) {
+    check_nhwc(*residual);
+    TORCH_CHECK(residual->scalar_type() == x.scalar_type(),
+                "bn residual must match input dtype");
+    TORCH_CHECK(residual->size(0) == N && residual->size(1) == C &&
+                residual->size(2) == H + 2 * res_pad &&
+                residual->size(3) == W + 2 * res_pad,
+                "bn residual geometry mismatch for res_pad=", res_pad);
+  }
   auto fopts = x.options().dtype(at::kFloat);
   auto save_mean = at::empty({C}, fopts);
   auto save_invstd = at::empty({C}, fopts);
@@ -457,14 +513,10 @@ std::vector<at::Tensor> fedkit_bn_fwd(const at::Tensor& x,
   auto stream = fedkit_stream();
   auto gamma_f = gamma.contiguous();
   auto beta_f = beta.contiguous();
-  TORCH_CHECK(gamma_f.scalar_type() == at::kFloat, "bn gamma must be fp32");
 
-  if (training && conv_part.has_value()) {
+  if (from_conv) {
     // stage 1 already happened inside the producing conv's epilogue
     auto& cp = *conv_part;
-    TORCH_CHECK(cp.scalar_type() == at::kFloat && cp.dim() == 4 &&
-                cp.size(0) * 64 == C && cp.size(2) == 2 && cp.size(3) == 64,
-                "bad conv_part shape for C=", C);
     bool track = running_mean.defined();
     int nwaves = 4;
     hipLaunchKernelGGL(bn_conv_colsum_finalize_kernel,
@@ -478,9 +530,6 @@ std::vector<at::Tensor> fedkit_bn_fwd(const at::Tensor& x,
   } else if (training) {
     DISPATCH_F32_BF16(x, "bn_partials", {
       constexpr int VEC = 16 / sizeof(scalar_t);
-      TORCH_CHECK(C % VEC == 0 && 256 % (C / VEC) == 0,
-                  "bn kernel needs C % ", VEC, " == 0 and (C/", VEC,
-                  ") | 256, got C=", C);
       int nb = grid_1d(M * C / VEC, 256, 512);
       auto part = at::empty({nb, 2, C}, fopts);
       hipLaunchKernelGGL((bn_partials_kernel<scalar_t, VEC>),
@@ -508,18 +557,9 @@ std::vector<at::Tensor> fedkit_bn_fwd(const at::Tensor& x,
   const bool has_res = residual.has_value();
   const void* res_ptr = nullptr;
   const int rpad = (int)res_pad;
-  if (has_res) {
-    check_nhwc(*residual);
-    TORCH_CHECK(residual->scalar_type() == x.scalar_type(),
-                "bn residual must match input dtype");
-    TORCH_CHECK(residual->size(2) == H + 2 * rpad &&
-                residual->size(3) == W + 2 * rpad,
-                "bn residual geometry mismatch for res_pad=", rpad);
-    res_ptr = residual->data_ptr();
-  }
+  if (has_res) res_ptr = residual->data_ptr();
   DISPATCH_F32_BF16(x, "bn_apply", {
     constexpr int VEC = 16 / sizeof(scalar_t);
-    TORCH_CHECK(C % VEC == 0, "bn needs C % ", VEC, " == 0");
     PadGeom pg = {H, W, H + 2 * pad, W + 2 * pad, pad};
     PadGeom rpg = {H, W, H + 2 * rpad, W + 2 * rpad, rpad};
     long long nvec = (pad == 0 ? M
@@ -563,8 +603,12 @@ std::vector<at::Tensor> fedkit_bn_bwd(const at::Tensor& gy, const at::Tensor& x,
   PadGeom pg = {H, W, H + 2 * pad, W + 2 * pad, pad};
   TORCH_CHECK(gy.size(2) == H && gy.size(3) == W,
               "bn_bwd: gy must be unpadded");
-  TORCH_CHECK(!pad || (elu_y.has_value() && elu_y->size(2) == pg.Hp),
-              "bn_bwd: elu_y geometry mismatch for pad_in=", pad);
+  TORCH_CHECK(pad >= 0 && (!pad || elu_y.has_value()),
+              "bn_bwd: pad_in needs the saved fused-ELU output elu_y");
+  TORCH_CHECK(!elu_y.has_value() ||
+              (elu_y->size(2) == pg.Hp && elu_y->size(3) == pg.Wp &&
+               elu_y->scalar_type() == x.scalar_type()),
+              "bn_bwd: elu_y geometry/dtype mismatch for pad_in=", pad);
   auto fopts = x.options().dtype(at::kFloat);
   auto ws = at::empty({2, C}, fopts);
   auto gx = at::empty_like(x);

@@ -1032,9 +1032,14 @@ void check_conv_inputs(const at::Tensor& x, const at::Tensor& w) {
 // (VAE/CPC shapes): y is allocated and stored dense at Ktrue channels.
 // vpad != nullptr: xp is the RAW gy (bwd-data) and the kernel performs the
 // dilate+pad virtually in the A stage (requires C % 64 == 0, stride 1).
+// bnpart != nullptr: run the MODE-1 epilogue and hand back its BatchNorm
+// partials slab [Kout/64][gridDim.x][2][64] through *bnpart.  The slab is
+// allocated HERE, after BM (and with it gridDim.x) is chosen, because the
+// epilogue indexes it by gridDim.x: this is the only place that knows the
+// tile-row count, whatever the threshold or FEDKIT_CONV_BM64 say.
 at::Tensor conv_core(const at::Tensor& xp, const at::Tensor& w_krs_c,
                      int stride, int P, int Q, int dil = 1, int Ktrue = -1,
-                     float* bnpart = nullptr,
+                     at::Tensor* bnpart = nullptr,
                      const VPadDesc* vpad = nullptr,
                      int bm64_below = 256 /* FWD callers pass 512 */) {
   int N = xp.size(0), C = xp.size(1), Hp = xp.size(2), Wp = xp.size(3);
@@ -1076,7 +1081,14 @@ at::Tensor conv_core(const at::Tensor& xp, const at::Tensor& w_krs_c,
       splits *= 2;
   }
   at::Tensor part;
-  float* aux = bnpart;
+  float* aux = nullptr;
+  if (bnpart) {
+    TORCH_CHECK(Ktrue == Kout && !vpad,
+                "conv BN-stats epilogue needs dense Kout and no virtual pad");
+    *bnpart = at::empty({(long long)grid.y, (long long)grid.x, 2, BN},
+                        xp.options().dtype(at::kFloat));
+    aux = bnpart->data_ptr<float>();
+  }
   if (splits > 1) {
     part = at::empty({splits, M, (long long)Kout},
                      xp.options().dtype(at::kFloat));
@@ -1268,7 +1280,8 @@ at::Tensor fedkit_conv2d_fwd_prepadded(const at::Tensor& xp,
 }
 
 // prepadded forward that ALSO emits the BatchNorm stage-1 partials
-// ([Kout/64][mtiles][2][64] fp32) from the epilogue registers — feeds
+// ([Kout/64][mtiles][2][64] fp32, mtiles = the tile rows conv_core
+// launched) from the epilogue registers — feeds
 // fedkit_bn_fwd's conv_part fast path (one launch and one full read of y
 // fewer per conv+BN pair).
 std::vector<at::Tensor> fedkit_conv2d_fwd_prepadded_bnstats(
@@ -1276,16 +1289,12 @@ std::vector<at::Tensor> fedkit_conv2d_fwd_prepadded_bnstats(
   check_conv_inputs(xp, w);
   int Hp = xp.size(2), Wp = xp.size(3);
   int R = w.size(2), S = w.size(3);
-  int Kout = w.size(0);
   int P = (Hp - R) / (int)stride + 1;
   int Q = (Wp - S) / (int)stride + 1;
-  long long M = (long long)xp.size(0) * P * Q;
-  bool bm64 = ((M + 127) / 128) * (Kout / BN) < 256;
-  long long mtiles = (M + (bm64 ? 63 : 127)) / (bm64 ? 64 : 128);
-  auto part = at::empty({Kout / BN, mtiles, 2, 64},
-                        xp.options().dtype(at::kFloat));
-  auto y = conv_core(xp, w, (int)stride, P, Q, 1, -1,
-                     part.data_ptr<float>(), nullptr, 512);
+  // conv_core picks the tile size and sizes the slab to the grid it
+  // launches (no second copy of the tile rule here)
+  at::Tensor part;
+  auto y = conv_core(xp, w, (int)stride, P, Q, 1, -1, &part, nullptr, 512);
   return {y, part};
 }
 
