@@ -19,17 +19,24 @@
 //   K-loop: STAGE(next) || ds_read+MFMA(cur) || vmcnt(0)+barrier.
 //
 // bwd-data reuses this kernel: dx = conv_s1(dilate_pad(dy), rot180(w)^T)
-// (host-side transform kernels below).  bwd-weight = im2col + rocBLAS GEMM
-// for now (dy^T @ xcol is a plain library GEMM; a hand-written tr_b16
-// MFMA bwd-weight kernel is the planned replacement).
+// (host-side transform kernels below).  bwd-weight transposes both operands
+// once and runs an implicit-GEMM MFMA kernel (dw_gemm_kernel); shapes it
+// does not cover take im2col + a library GEMM.
 //
-// Constraints (host-checked): C % 8 == 0, (R*S*C) % 64 == 0, Kout % 64 == 0,
-// bf16 tensors.  conv1 of ResNet (C=3) uses the dedicated direct kernel in
-// conv_small.hip.
+// Every tile / split / variant choice is made by conv_plan.h (plain
+// integers, tested without a GPU); the host wrappers here only turn a plan
+// into a launch through one table per kernel family.
+//
+// Constraints (host-checked): C % 8 == 0, Kout % 64 == 0, bf16 tensors (a
+// Kg = R*S*C tail tile is zero-filled).  conv1 of ResNet (C=3) uses the
+// dedicated direct kernel in conv_small.hip.
 
 #include "fedkit_common.h"
+#include "conv_plan.h"
 
 namespace {
+
+using namespace fedkit_plan;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -39,8 +46,8 @@ typedef __hip_bfloat16 bf16;
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr), \
                                    (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
-constexpr int BN = 64;   // out-channel tile
-constexpr int BK = 64;   // im2col-k tile
+constexpr int BN = kBN;  // out-channel tile
+constexpr int BK = kBK;  // im2col-k tile
 
 // 16-B zero page for the Kg tail: when Kg % 64 != 0 (Net-family 5x5 and
 // valid-3x3 shapes: Kg = 200 / 72 / 288) the last K-tile's out-of-range
@@ -93,8 +100,7 @@ __device__ __forceinline__ int lds_off(int row, int k) {
 // STAGES: 3 = double-lookahead pipeline (72 KB LDS at BM=128 -> 2 wg/CU);
 // 2 = single-lookahead (48 KB -> 3 wg/CU: PMC shows 43% wave-wait at
 // occupancy 2 with zero LDS conflicts, so more resident waves may hide
-// more latency than the deeper pipeline) — picked per measurement via
-// FEDKIT_CONV_STAGES.
+// more latency than the deeper pipeline) — picked per form by plan_conv.
 // VPAD: 0 = pre-materialized input; 1 = virtual pad, stride-1 source
 // (per-slot int compares, affine address); 2 = virtual pad over a
 // stride-2 zero-inserted source (bwd-data of stride-2 convs): the A
@@ -102,8 +108,7 @@ __device__ __forceinline__ int lds_off(int row, int k) {
 // buffer, it skips the 3/4-zeros A traffic the materialized dilated
 // image pays.  Parity/bounds per slot via 2 precomputed parity bits and
 // 4 stage-scalar class offsets (no 64-bit muls in the loop).
-template <int BM, int STRIDE, int MODE, int STAGES, bool MT = false,
-          int VPAD = 0>
+template <int BM, int STRIDE, int MODE, int STAGES, bool MT, int VPAD>
 __global__ __launch_bounds__(256)
 void conv_fwd_kernel(const bf16* __restrict__ xp,  // [N][Hp][Wp][C] padded
                      const bf16* __restrict__ w,   // [Kout][R*S*C]
@@ -113,8 +118,7 @@ void conv_fwd_kernel(const bf16* __restrict__ xp,  // [N][Hp][Wp][C] padded
                      int Ktrue /* <= Kout: K rows beyond are zero-padding
                                   (VAE/CPC channel counts), skipped on
                                   store so y needs no unpad pass */,
-                     float* __restrict__ aux, TapDesc td = {},
-                     VPadDesc vp = {}) {
+                     float* __restrict__ aux, TapDesc td, VPadDesc vp) {
   constexpr int AB = BM * BK * 2;          // A tile bytes
   constexpr int BB = BN * BK * 2;          // B tile bytes
   __shared__ char smem[STAGES * (AB + BB)];
@@ -448,8 +452,8 @@ void conv_fwd_kernel(const bf16* __restrict__ xp,  // [N][Hp][Wp][C] padded
 // materializing im2col + a library split-K GEMM (extra HBM round-trips),
 // both operands are TRANSPOSED ONCE with an LDS-tiled transpose:
 //
-//   dyT [K][M]          <- dy  [M][K]      (transpose_mk_kernel)
-//   xpT [C][N][Hp][Wp]  <- xp  [N][Hp][Wp][C]   (same kernel, M' = N*Hp*Wp)
+//   dyT [K][M]          <- dy  [M][K]      (transpose_mk_batch_kernel)
+//   xpT [C][N][Hp][Wp]  <- xp  [N][Hp][Wp][C]   (same launch, M' = N*Hp*Wp)
 //
 // and the GEMM reads its B operand IMPLICITLY from xpT: for a fixed
 // (r, s, c) row, 8 consecutive m are 8 consecutive q, which in xpT is 16
@@ -458,9 +462,9 @@ void conv_fwd_kernel(const bf16* __restrict__ xp,  // [N][Hp][Wp][C] padded
 // kernel.  Output: fp32 partials [SPLITS][K][RSC] (one m-slice per split),
 // column-summed to bf16 by colsum_to_bf16_kernel.
 //
-// Qualifying shapes (host-checked): stride 1, Q % 8 == 0, P/Q powers of two,
-// K % 64 == 0, RSC % 64 == 0, M % 64 == 0 — i.e. 13 of the 17 ResNet18
-// convs, carrying ~80 % of dw cost.  Everything else takes the im2col +
+// Qualifying shapes: plan_dw's `fast` (Q % 8 == 0, P/Q powers of two,
+// K, C, M multiples of 64; stride 2 through even/odd-column planes) —
+// 15 of the 17 ResNet18 convs.  Everything else takes the im2col +
 // split-K library-GEMM path below.
 
 // LDS-tiled 64x64 bf16 transpose: out[k][m] = in[m][k].  Both global phases
@@ -472,72 +476,31 @@ __device__ __forceinline__ int tr_off(int row, int k) {
   return row * 128 + chunk * 16 + (k & 7) * 2;
 }
 
-// mscale/moff subsample the input rows (out[k][m'] = in[m'*mscale+moff][k])
-// — used to build the even/odd-column planes for the stride-2 dw path.
-__global__ __launch_bounds__(256)
-void transpose_mk_kernel(const bf16* __restrict__ in,  // [M][K]
-                         bf16* __restrict__ out,       // [K][M]
-                         long long M, int K, long long mscale,
-                         long long moff) {
-  __shared__ char smem[64 * 128];
-  const int tid = threadIdx.x;
-  const long long mt = (long long)blockIdx.x * 64;
-  const int kt = blockIdx.y * 64;
+// load phase of a 64x64 tile: LDS row = input row, 8 contiguous columns per
+// lane; src(row) points at the row's first column
+template <typename Src>
+__device__ __forceinline__ void tr_load64(char* smem, int tid, Src src) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {            // load: row = m, 8 k per lane
+  for (int i = 0; i < 2; ++i) {
     int d = i * 256 + tid;
     int row = d >> 3, c = d & 7;
-    *(bf16x8*)(smem + tr_off(row, c * 8)) =
-        *(const bf16x8*)(in + ((mt + row) * mscale + moff) * K + kt + c * 8);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {            // store: row = k, 8 m per lane
-    int d = i * 256 + tid;
-    int kr = d >> 3, c = d & 7;
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      v[j] = *(const bf16*)(smem + tr_off(c * 8 + j, kr));
-    *(bf16x8*)(out + (long long)(kt + kr) * M + mt + c * 8) = v;
+    *(bf16x8*)(smem + tr_off(row, c * 8)) = *(const bf16x8*)(src(row) + c * 8);
   }
 }
 
-// Packed-Q plane transpose (layer4-class dw, Q == 4): out[k][m'] where
-// m' walks an [Nh][4] plane and the source pixel is
-//   m_in = (m' >> 2) * rowstride + rowoff + (m' & 3) * cs
-// i.e. 4 filter-column-aligned pixels per source row, rows subsampled by
-// rowstride (h-parity planes for stride 2).  After this, an 8-m' chunk =
-// TWO consecutive plane rows = the two output rows a Q=4 m-chunk spans —
-// contiguous 16 B, so the dw GEMM's glds staging applies unchanged.
-__global__ __launch_bounds__(256)
-void transpose_pack_kernel(const bf16* __restrict__ in,  // [Mfull][K]
-                           bf16* __restrict__ out,       // [K][Mp]
-                           long long Mp, int K, long long rowstride,
-                           long long rowoff, int cs) {
-  __shared__ char smem[64 * 128];
-  const int tid = threadIdx.x;
-  const long long mt = (long long)blockIdx.x * 64;
-  const int kt = blockIdx.y * 64;
+// store phase: output row = input column, 8 input rows gathered per lane;
+// dst(row) points at the output row's first element
+template <typename Dst>
+__device__ __forceinline__ void tr_store64(const char* smem, int tid, Dst dst) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {            // load: row = m', 8 k per lane
+  for (int i = 0; i < 2; ++i) {
     int d = i * 256 + tid;
     int row = d >> 3, c = d & 7;
-    long long mp = mt + row;
-    long long m_in = (mp >> 2) * rowstride + rowoff + (mp & 3) * cs;
-    *(bf16x8*)(smem + tr_off(row, c * 8)) =
-        *(const bf16x8*)(in + m_in * K + kt + c * 8);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {            // store: row = k, 8 m' per lane
-    int d = i * 256 + tid;
-    int kr = d >> 3, c = d & 7;
     bf16x8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      v[j] = *(const bf16*)(smem + tr_off(c * 8 + j, kr));
-    *(bf16x8*)(out + (long long)(kt + kr) * Mp + mt + c * 8) = v;
+      v[j] = *(const bf16*)(smem + tr_off(c * 8 + j, row));
+    *(bf16x8*)(dst(row) + c * 8) = v;
   }
 }
 
@@ -545,9 +508,11 @@ void transpose_pack_kernel(const bf16* __restrict__ in,  // [Mfull][K]
 // xpT[+ xpT2]) issued as a SINGLE launch — each costs ~6 us of which most
 // is launch/ramp latency at these sizes (~32 transpose launches/step,
 // ~190 us, round-2 profile).  1-D grid linearizes all jobs' 64x64 tiles.
+// mscale/moff subsample the input rows (out[k][m'] = in[m'*mscale+moff][k])
+// — used to build the even/odd-column planes for the stride-2 dw path.
 struct TransJob {
-  const bf16* in;
-  bf16* out;
+  const bf16* in;           // [M*mscale][K]
+  bf16* out;                // [K][M]
   long long M;
   int K;
   long long mscale, moff;
@@ -568,25 +533,13 @@ void transpose_mk_batch_kernel(TransJob j0, TransJob j1, TransJob j2,
   const long long mtiles = j.M / 64;
   const long long mt = (rel % mtiles) * 64;
   const int kt = (int)(rel / mtiles) * 64;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int d = i * 256 + tid;
-    int row = d >> 3, c = d & 7;
-    *(bf16x8*)(smem + tr_off(row, c * 8)) =
-        *(const bf16x8*)(j.in + ((mt + row) * j.mscale + j.moff) * j.K +
-                         kt + c * 8);
-  }
+  tr_load64(smem, tid, [&](int row) {
+    return j.in + ((mt + row) * j.mscale + j.moff) * j.K + kt;
+  });
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int d = i * 256 + tid;
-    int kr = d >> 3, c = d & 7;
-    bf16x8 v;
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj)
-      v[jj] = *(const bf16*)(smem + tr_off(c * 8 + jj, kr));
-    *(bf16x8*)(j.out + (long long)(kt + kr) * j.M + mt + c * 8) = v;
-  }
+  tr_store64(smem, tid, [&](int kr) {
+    return j.out + (long long)(kt + kr) * j.M + mt;
+  });
 }
 
 // Vectorized bwd-data weight rotation: wrot[c][R-1-r][S-1-s][k] =
@@ -603,30 +556,19 @@ void rot_weight64_kernel(const bf16* __restrict__ w,   // [K][R*S*C]
   const int kt = blockIdx.x * 64;          // k tile (input rows)
   const int jt = blockIdx.y * 64;          // rsc tile (input cols)
   const int RSC = R * S * C;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {            // load: row = k, 8 rsc per lane
-    int d = i * 256 + tid;
-    int row = d >> 3, c = d & 7;
-    *(bf16x8*)(smem + tr_off(row, c * 8)) =
-        *(const bf16x8*)(w + (long long)(kt + row) * RSC + jt + c * 8);
-  }
+  tr_load64(smem, tid, [&](int row) {
+    return w + (long long)(kt + row) * RSC + jt;
+  });
   __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {            // store: row = rsc (permuted), 8 k
-    int d = i * 256 + tid;
-    int jr = d >> 3, c = d & 7;
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      v[j] = *(const bf16*)(smem + tr_off(c * 8 + j, jr));
+  tr_store64(smem, tid, [&](int jr) {
     int rsc = jt + jr;
     int cc = rsc % C;
     int rs = rsc / C;
     int s = rs % S;
     int r = rs / S;
     long long o = ((long long)cc * R + (R - 1 - r)) * S + (S - 1 - s);
-    *(bf16x8*)(wr + o * K + kt + c * 8) = v;
-  }
+    return wr + o * K + kt;
+  });
 }
 
 // dw GEMM on the transposed operands: D[kout][rsc] += A[kout][m] B[rsc][m]
@@ -635,11 +577,10 @@ void rot_weight64_kernel(const bf16* __restrict__ w,   // [K][R*S*C]
 // BMK (kout tile) = 128 where K allows — the 64x64 tile has half the MFMA
 // work per LDS read and measured ~1.7x slower — else 64; grid.z splits the
 // m range into independent fp32 partials.
-// BGLDS=1 stages B via LDS-DMA straight from the (only 2-B aligned) xpT
-// rows.  Measured on gfx950: unaligned global_load_lds is CORRECT (all
-// numerics tests pass) and 34-40 % faster than register staging + ds_write
-// (layer3 dw 64.6 -> 38.8 us) — the default; FEDKIT_DW_GLDSB=0 falls back
-// to the alignment-safe register path.
+// B stages via LDS-DMA straight from the (only 2-B aligned) xpT rows.
+// Measured on gfx950: unaligned global_load_lds is CORRECT (all numerics
+// tests pass) and 34-40 % faster than register staging + ds_write (layer3
+// dw 64.6 -> 38.8 us).
 // STRIDE=2 reads from TWO half-width transposed planes (even/odd input
 // columns): 8 consecutive output q stay contiguous within the plane of
 // the filter column's parity, so the same glds staging applies; Wp is the
@@ -647,21 +588,9 @@ void rot_weight64_kernel(const bf16* __restrict__ w,   // [K][R*S*C]
 // NT=2 doubles the rsc tile (two B tiles share one A stage: 8 MFMAs per
 // 6 LDS reads instead of 4 per 4) — used for layer1 (K=64 caps the kout
 // tile at 64 and its 48.8 us was the largest single kernel).
-// QH=1 handles Q == 4 (layer4-class shapes): an 8-m chunk spans TWO
-// output rows (q 0..3 of p and of p+1), staged as two 8-byte register
-// loads — LDS-DMA cannot compose two pieces into one 16-B/lane image, so
-// these shapes force the register-staging commit path.
-// QP != 0: packed-Q planes (Q == 4 shapes).  xpT/xpT2 are unused; the B
-// operand reads from ps.p[...]: QP=1 (fwd stride 1) plane s, row r;
-// QP=2 (fwd stride 2) plane s*2 + (r&1), row r>>1 (h-parity split).  In
-// both cases plane layout is [C][N][Hp_pl][4] and the m-chunk addressing
-// is the plain STRIDE=1 form with Wp = 4 — the plane construction
-// absorbed the filter column and the stride.
-struct PlaneSet {
-  const bf16* p[6];
-};
-
-template <int BMK, int BGLDS, int STRIDE, int NT = 1, int QH = 0, int QP = 0>
+// (Two Q == 4 variants and a register-staged B were measured slower and
+// removed — NOTES.md, "Measured dead ends".)
+template <int BMK, int STRIDE, int NT>
 __global__ __launch_bounds__(256)
 void dw_gemm_kernel(const bf16* __restrict__ dyT,  // [K][M]
                     const bf16* __restrict__ xpT,  // [C][N][Hp][Wp(lane)]
@@ -670,8 +599,7 @@ void dw_gemm_kernel(const bf16* __restrict__ dyT,  // [K][M]
                     int K, int C, int N, int Hp, int Wp, int S,
                     long long M, int RSC, int mtiles_per_split,
                     int qshift /* log2 Q */, int qmask,
-                    int pshift /* log2 (P*Q) */, int pmask,
-                    PlaneSet ps = {}) {
+                    int pshift /* log2 (P*Q) */, int pmask) {
   constexpr int BNT = BN * NT;             // rsc tile rows
   constexpr int AB = BMK * BK * 2;         // A tile bytes
   constexpr int BB = BNT * BK * 2;         // B tile bytes
@@ -714,13 +642,7 @@ void dw_gemm_kernel(const bf16* __restrict__ dyT,  // [K][M]
     int rs = rsc / C;
     int s = rs % S;
     int r = rs / S;
-    if (QP == 1) {
-      b_plane[i] = ps.p[s];
-      b_base[i] = ((long long)c * N * Hp + r) * Wp;
-    } else if (QP == 2) {
-      b_plane[i] = ps.p[s * 2 + (r & 1)];
-      b_base[i] = ((long long)c * N * Hp + (r >> 1)) * Wp;
-    } else if (STRIDE == 2) {
+    if (STRIDE == 2) {
       b_plane[i] = (s & 1) ? xpT2 : xpT;
       b_base[i] = ((long long)c * N * Hp + r) * Wp + (s >> 1);
     } else {
@@ -732,13 +654,9 @@ void dw_gemm_kernel(const bf16* __restrict__ dyT,  // [K][M]
   auto bufA = [&](int b) -> char* { return smem + b * (AB + BB); };
   auto bufB = [&](int b) -> char* { return smem + b * (AB + BB) + AB; };
 
-  // A (dyT rows, always 16-B aligned) stages via glds; B (xpT rows shifted by
-  // the filter column s, so only 2-B aligned) REGISTER-stages: an
-  // unaligned-capable global vector load into VGPRs, committed to LDS with
-  // ds_write_b128 right before the barrier (guide T14 — ties glds within a
-  // few %, and sidesteps the LDS-DMA alignment question entirely).
-  bf16x8 breg[2][BS];
-  auto stage = [&](int buf, int kt, bf16x8* br) {
+  // A (dyT rows, always 16-B aligned) and B (xpT rows shifted by the filter
+  // column s, so only 2-B aligned) both stage via glds
+  auto stage = [&](int buf, int kt) {
     const long long mt = m0 + (long long)kt * BK;
 #pragma unroll
     for (int i = 0; i < A_SLOTS; ++i) {
@@ -753,22 +671,8 @@ void dw_gemm_kernel(const bf16* __restrict__ dyT,  // [K][M]
       int n = (int)(mm >> pshift);
       const bf16* src =
           b_plane[i] + b_base[i] + ((long long)n * Hp + p * STRIDE) * Wp + q;
-      if (QH) {
-        // q == 0 here (chunks are 8-aligned, Q == 4): rows p and p+1
-        __builtin_memcpy(&br[i], src, 8);
-        __builtin_memcpy(reinterpret_cast<char*>(&br[i]) + 8,
-                         src + (long long)STRIDE * Wp, 8);
-      } else if (BGLDS) {
-        GLDS16(src, bufB(buf) + (i * 4 + wave) * 1024);
-      } else {
-        __builtin_memcpy(&br[i], src, sizeof(bf16x8));
-      }
+      GLDS16(src, bufB(buf) + (i * 4 + wave) * 1024);
     }
-  };
-  auto commitB = [&](int buf, const bf16x8* br) {
-#pragma unroll
-    for (int i = 0; i < BS; ++i)
-      *(bf16x8*)(bufB(buf) + (i * 4 + wave) * 1024 + lane * 16) = br[i];
   };
 
   constexpr int MR = BMK / 2 / 16;         // kout frags per wave (2 or 4)
@@ -780,22 +684,16 @@ void dw_gemm_kernel(const bf16* __restrict__ dyT,  // [K][M]
   const int wr = (wave & 1) * (BNT / 2);
 
   if (nkt > 0) {
-    stage(0, 0, breg[0]);
-    if (nkt > 1) stage(1, 1, breg[1]);
+    stage(0, 0);
+    if (nkt > 1) stage(1, 1);
     for (int kt = 0; kt < nkt; ++kt) {
-      // drain stage kt's VMEM ops (A_SLOTS glds + the B loads — two
-      // 8-byte pieces per slot under QH); stage kt+1's stay in flight
-      constexpr int BOPS = (QH ? 2 : 1) * BS;
+      // drain stage kt's glds ops (A_SLOTS + BS); stage kt+1's stay in flight
       if (kt + 1 < nkt)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_SLOTS + BOPS) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_SLOTS + BS) : "memory");
       else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (!BGLDS) {
-        commitB(kt % 3, breg[kt % 2]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
       __builtin_amdgcn_s_barrier();
-      if (kt + 2 < nkt) stage((kt + 2) % 3, kt + 2, breg[kt % 2]);
+      if (kt + 2 < nkt) stage((kt + 2) % 3, kt + 2);
       const char* A = bufA(kt % 3);
       const char* B = bufB(kt % 3);
 #pragma unroll
@@ -866,8 +764,6 @@ __global__ void colsum_stage_kernel(const float* __restrict__ part,
 }
 
 // ---------------------------------------------------------------- transforms
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16v8;
 
 // OUTPUT-indexed zero-pad/dilate NHWC, 16 B/lane (8 bf16 = one C-chunk;
 // VEC=1 scalar fallback for C % 8 != 0, e.g. conv1's C=3):
@@ -979,7 +875,8 @@ __global__ void dilate_pad_out3d_kernel(const bf16* __restrict__ in,
   }
 }
 
-at::Tensor dilate_pad_core(const at::Tensor& x, int pt, int pb, int pl,
+// str = 1 is plain zero padding
+at::Tensor dilate_pad_nhwc(const at::Tensor& x, int pt, int pb, int pl,
                            int pr, int str) {
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   int Hp = (H - 1) * str + 1 + pt + pb, Wp = (W - 1) * str + 1 + pl + pr;
@@ -1008,13 +905,8 @@ at::Tensor dilate_pad_core(const at::Tensor& x, int pt, int pb, int pl,
   return xp;
 }
 
-at::Tensor pad_nhwc(const at::Tensor& x, int pt, int pb, int pl, int pr) {
-  return dilate_pad_core(x, pt, pb, pl, pr, 1);
-}
-
-at::Tensor dilate_pad_nhwc(const at::Tensor& x, int pt, int pb, int pl, int pr,
-                           int str) {
-  return dilate_pad_core(x, pt, pb, pl, pr, str);
+at::Tensor pad_nhwc(const at::Tensor& x, int pad) {
+  return pad > 0 ? dilate_pad_nhwc(x, pad, pad, pad, pad, 1) : x;
 }
 
 void check_conv_inputs(const at::Tensor& x, const at::Tensor& w) {
@@ -1027,6 +919,52 @@ void check_conv_inputs(const at::Tensor& x, const at::Tensor& w) {
               "conv weight must be channels_last");
 }
 
+// ---- plan -> kernel: one table per kernel family, expanded from the variant
+// lists in conv_plan.h (so exactly the listed kernels are instantiated)
+using ConvKernel = decltype(&conv_fwd_kernel<64, 1, 0, 2, false, 0>);
+struct ConvVariant {
+  int BM, stride, mode, stages;
+  bool mt;
+  int vpad;
+  ConvKernel kern;
+};
+#define X(bm, st, mode, stages, mt, vpad) \
+  {bm, st, mode, stages, mt, vpad,        \
+   conv_fwd_kernel<bm, st, mode, stages, mt, vpad>},
+const ConvVariant kConvVariants[] = {FEDKIT_CONV_VARIANTS(X)};
+#undef X
+
+using DwKernel = decltype(&dw_gemm_kernel<64, 1, 1>);
+struct DwVariant {
+  int BMK, stride, NT;
+  DwKernel kern;
+};
+#define X(bmk, st, nt) {bmk, st, nt, dw_gemm_kernel<bmk, st, nt>},
+const DwVariant kDwVariants[] = {FEDKIT_DW_VARIANTS(X)};
+#undef X
+
+struct ConvDims {
+  int N, Hp, Wp, C, Kout, R, S, P, Q, Kg, dil, Ktrue;
+};
+
+void launch_conv(const ConvPlan& p, const ConvDims& d, const at::Tensor& xp,
+                 const at::Tensor& w, at::Tensor& y, float* aux,
+                 const TapDesc& td, const VPadDesc& vp) {
+  ConvKernel kern = nullptr;
+  for (const ConvVariant& v : kConvVariants)
+    if (v.BM == p.BM && v.stride == p.stride && v.mode == p.mode &&
+        v.stages == p.stages && v.mt == p.multitap && v.vpad == p.vpad)
+      kern = v.kern;
+  TORCH_CHECK(kern, "no conv_fwd_kernel for plan BM=", p.BM, " stride=",
+              p.stride, " mode=", p.mode, " stages=", p.stages, " multitap=",
+              p.multitap, " vpad=", p.vpad);
+  hipLaunchKernelGGL(kern, dim3(p.grid_x, p.grid_y, p.splits), dim3(256), 0,
+                     fedkit_stream(), (const bf16*)xp.data_ptr(),
+                     (const bf16*)w.data_ptr(), (bf16*)y.data_ptr(), d.N,
+                     d.Hp, d.Wp, d.C, d.Kout, d.R, d.S, d.P, d.Q, d.Kg, d.dil,
+                     d.Ktrue, aux, td, vp);
+}
+
 // launch on the PRE-PADDED input; pad already folded into Hp/Wp.
 // Ktrue < Kout means the trailing weight rows are channel zero-padding
 // (VAE/CPC shapes): y is allocated and stored dense at Ktrue channels.
@@ -1034,14 +972,12 @@ void check_conv_inputs(const at::Tensor& x, const at::Tensor& w) {
 // dilate+pad virtually in the A stage (requires C % 64 == 0, stride 1).
 // bnpart != nullptr: run the MODE-1 epilogue and hand back its BatchNorm
 // partials slab [Kout/64][gridDim.x][2][64] through *bnpart.  The slab is
-// allocated HERE, after BM (and with it gridDim.x) is chosen, because the
-// epilogue indexes it by gridDim.x: this is the only place that knows the
-// tile-row count, whatever the threshold or FEDKIT_CONV_BM64 say.
+// allocated HERE, from the plan's grid, because the epilogue indexes it by
+// gridDim.x: no caller holds a tile rule.
 at::Tensor conv_core(const at::Tensor& xp, const at::Tensor& w_krs_c,
-                     int stride, int P, int Q, int dil = 1, int Ktrue = -1,
-                     at::Tensor* bnpart = nullptr,
-                     const VPadDesc* vpad = nullptr,
-                     int bm64_below = 256 /* FWD callers pass 512 */) {
+                     int stride, int P, int Q, ConvCaller caller, int dil = 1,
+                     int Ktrue = -1, at::Tensor* bnpart = nullptr,
+                     const VPadDesc* vpad = nullptr) {
   int N = xp.size(0), C = xp.size(1), Hp = xp.size(2), Wp = xp.size(3);
   int Kout = w_krs_c.size(0), R = w_krs_c.size(2), S = w_krs_c.size(3);
   int Kg = R * S * C;
@@ -1050,141 +986,63 @@ at::Tensor conv_core(const at::Tensor& xp, const at::Tensor& w_krs_c,
   // Kg % 64 != 0 is allowed: the kernel zero-fills the tail K-tile from a
   // device zero page (Net-family 5x5 / valid-3x3 shapes)
   TORCH_CHECK(Kout % BN == 0, "conv kernel needs Kout % 64 == 0, got ", Kout);
+  TORCH_CHECK(stride == 1 || stride == 2, "conv kernel supports stride 1/2");
+  TORCH_CHECK(!bnpart || (Ktrue == Kout && !vpad),
+              "conv BN-stats epilogue needs dense Kout and no virtual pad");
+  TORCH_CHECK(!vpad || (C % 64 == 0 && stride == 1),
+              "vpad path needs C % 64 == 0, stride-1 conv");
   long long M = (long long)N * P * Q;
+  const ConvPlan p = plan_conv(M, Kout, Kg, stride, Ktrue == Kout,
+                               bnpart != nullptr, vpad ? vpad->vstr : 0,
+                               caller);
   auto y = at::empty({N, Ktrue, P, Q},
                      xp.options().memory_format(at::MemoryFormat::ChannelsLast));
-  auto stream = fedkit_stream();
-  // pick BM so the grid fills the 256 CUs when possible
-  // (FEDKIT_CONV_BM64=1 forces the 64-row tile everywhere: tuning knob —
-  // half the MFMA density per wg but 2x the workgroups and 3 wg/CU)
-  static const int force_bm64 = []() {
-    const char* e = getenv("FEDKIT_CONV_BM64");
-    return e ? atoi(e) : 0;
-  }();
-  // per-call-site threshold: FWD shapes measured BM64 wins below 512 wgs
-  // (C128-s2 fwd 20.5 -> 15.2 us, fwd_sweep.log) but BOTH bwd-data forms
-  // regressed under it (vpad layer3 dx 32.4 -> 49.8, materialized s2-C256
-  // 52.4 -> 64.0) — backward callers keep the 256 default.
-  bool bm64 = force_bm64 ||
-      ((M + 127) / 128) * (Kout / BN) < (vpad ? 256 : bm64_below);
-  int BM = bm64 ? 64 : 128;
-  dim3 grid((unsigned)((M + BM - 1) / BM), Kout / BN);
-  TORCH_CHECK(stride == 1 || stride == 2, "conv kernel supports stride 1/2");
-  // split-K when the (M, Kout) grid alone cannot fill the 256 CUs and the
-  // Kg loop is deep enough to slice (layer4-class shapes)
-  int gridxy = (int)grid.x * (int)grid.y;
-  int nkt_total = (Kg + BK - 1) / BK;
-  int splits = 1;
-  if (!bnpart && Ktrue == Kout && gridxy <= 256) {
-    while (splits < 8 && gridxy * splits < 512 &&
-           nkt_total / (splits * 2) >= 4)
-      splits *= 2;
-  }
   at::Tensor part;
   float* aux = nullptr;
   if (bnpart) {
-    TORCH_CHECK(Ktrue == Kout && !vpad,
-                "conv BN-stats epilogue needs dense Kout and no virtual pad");
-    *bnpart = at::empty({(long long)grid.y, (long long)grid.x, 2, BN},
+    *bnpart = at::empty({(long long)p.grid_y, (long long)p.grid_x, 2, BN},
                         xp.options().dtype(at::kFloat));
     aux = bnpart->data_ptr<float>();
   }
-  if (splits > 1) {
-    part = at::empty({splits, M, (long long)Kout},
+  if (p.splits > 1) {
+    part = at::empty({p.splits, M, (long long)Kout},
                      xp.options().dtype(at::kFloat));
     aux = part.data_ptr<float>();
-    grid.z = splits;
   }
-  auto L = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
-                       (const bf16*)xp.data_ptr(),
-                       (const bf16*)w_krs_c.data_ptr(), (bf16*)y.data_ptr(),
-                       N, Hp, Wp, C, Kout, R, S, P, Q, Kg, dil, Ktrue,
-                       aux, TapDesc{}, vpad ? *vpad : VPadDesc{});
-  };
-  // STAGES=2 (single lookahead, 48 KB LDS -> 3 wg/CU) measured faster or
-  // tied on EVERY MODE-0 shape in the round-2 sweep (layer1 25.2 -> 22.6
-  // us; fwd_sweep.log) — the extra resident waves hide more latency than
-  // the deeper pipeline, consistent with the 43% wave-wait PMC.  Default
-  // 2; FEDKIT_CONV_STAGES=3 restores the old pipeline.
-  static const int stages3 = []() {
-    const char* e = getenv("FEDKIT_CONV_STAGES");
-    return e && atoi(e) == 3;
-  }();
-  const bool stages2 = !stages3;
-  if (vpad) {
-    TORCH_CHECK(C % 64 == 0 && stride == 1 && !bnpart,
-                "vpad path needs C % 64 == 0, stride-1 conv");
-    bool v2 = vpad->vstr == 2;
-    if (splits > 1) {
-      if (v2)
-        bm64 ? L(conv_fwd_kernel<64, 1, 2, 3, false, 2>)
-             : L(conv_fwd_kernel<128, 1, 2, 3, false, 2>);
-      else
-        bm64 ? L(conv_fwd_kernel<64, 1, 2, 3, false, 1>)
-             : L(conv_fwd_kernel<128, 1, 2, 3, false, 1>);
-      long long Ly = M * Kout;
-      hipLaunchKernelGGL(colsum_to_bf16_kernel, dim3(grid_1d(Ly, 256)),
-                         dim3(256), 0, stream, part.data_ptr<float>(),
-                         splits, Ly, (bf16*)y.data_ptr());
-    } else if (stages2) {
-      if (v2)
-        bm64 ? L(conv_fwd_kernel<64, 1, 0, 2, false, 2>)
-             : L(conv_fwd_kernel<128, 1, 0, 2, false, 2>);
-      else
-        bm64 ? L(conv_fwd_kernel<64, 1, 0, 2, false, 1>)
-             : L(conv_fwd_kernel<128, 1, 0, 2, false, 1>);
-    } else {
-      if (v2)
-        bm64 ? L(conv_fwd_kernel<64, 1, 0, 3, false, 2>)
-             : L(conv_fwd_kernel<128, 1, 0, 3, false, 2>);
-      else
-        bm64 ? L(conv_fwd_kernel<64, 1, 0, 3, false, 1>)
-             : L(conv_fwd_kernel<128, 1, 0, 3, false, 1>);
-    }
-    return y;
-  }
-  if (splits > 1) {
-    if (stages2) {
-      if (stride == 1)
-        bm64 ? L(conv_fwd_kernel<64, 1, 2, 2>) : L(conv_fwd_kernel<128, 1, 2, 2>);
-      else
-        bm64 ? L(conv_fwd_kernel<64, 2, 2, 2>) : L(conv_fwd_kernel<128, 2, 2, 2>);
-    } else if (stride == 1)
-      bm64 ? L(conv_fwd_kernel<64, 1, 2, 3>) : L(conv_fwd_kernel<128, 1, 2, 3>);
-    else
-      bm64 ? L(conv_fwd_kernel<64, 2, 2, 3>) : L(conv_fwd_kernel<128, 2, 2, 3>);
+  launch_conv(p, {N, Hp, Wp, C, Kout, R, S, P, Q, Kg, dil, Ktrue}, xp,
+              w_krs_c, y, aux, TapDesc{}, vpad ? *vpad : VPadDesc{});
+  if (p.splits > 1) {
     long long Ly = M * Kout;
     hipLaunchKernelGGL(colsum_to_bf16_kernel, dim3(grid_1d(Ly, 256)),
-                       dim3(256), 0, stream, part.data_ptr<float>(), splits,
-                       Ly, (bf16*)y.data_ptr());
-  } else if (bnpart) {
-    if (stride == 1)
-      bm64 ? L(conv_fwd_kernel<64, 1, 1, 3>) : L(conv_fwd_kernel<128, 1, 1, 3>);
-    else
-      bm64 ? L(conv_fwd_kernel<64, 2, 1, 3>) : L(conv_fwd_kernel<128, 2, 1, 3>);
-  } else if (stages2) {
-    if (stride == 1)
-      bm64 ? L(conv_fwd_kernel<64, 1, 0, 2>) : L(conv_fwd_kernel<128, 1, 0, 2>);
-    else
-      bm64 ? L(conv_fwd_kernel<64, 2, 0, 2>) : L(conv_fwd_kernel<128, 2, 0, 2>);
-  } else {
-    if (stride == 1)
-      bm64 ? L(conv_fwd_kernel<64, 1, 0, 3>) : L(conv_fwd_kernel<128, 1, 0, 3>);
-    else
-      bm64 ? L(conv_fwd_kernel<64, 2, 0, 3>) : L(conv_fwd_kernel<128, 2, 0, 3>);
+                       dim3(256), 0, fedkit_stream(), part.data_ptr<float>(),
+                       p.splits, Ly, (bf16*)y.data_ptr());
   }
   return y;
 }
 
 }  // namespace
 
+// the instantiated kernels, from the dispatch tables (coverage test)
+std::vector<std::vector<long>> fedkit_conv_variants() {
+  std::vector<std::vector<long>> out;
+  for (const ConvVariant& v : kConvVariants)
+    out.push_back({v.BM, v.stride, v.mode, v.stages, v.vpad, v.mt});
+  return out;
+}
+
+std::vector<std::vector<long>> fedkit_dw_variants() {
+  std::vector<std::vector<long>> out;
+  for (const DwVariant& v : kDwVariants)
+    out.push_back({v.BMK, v.stride, v.NT});
+  return out;
+}
+
 // Fused multi-dilation conv bank (CPC EncoderCNN, simple_models.py:441-460):
 // n_tap convs share one input and one launch.  x [N,C,H,W] NHWC bf16;
 // w2d [64, n_tap*R*R*C] bf16 contiguous BLOCK-DIAGONAL combined weight
 // (rows t*Kt .. per tap t nonzero only in its kg block, Kt true out
 // channels per tap); dils/pads per tap; all taps must produce the same
-// P x Q.  Returns [N, ktrue, P, Q] channels_last (the torch.cat result).
+// P x Q.  Returns [N, ktrue, P, P] channels_last (the torch.cat result).
 at::Tensor fedkit_conv2d_dilated_bank(const at::Tensor& x,
                                       const at::Tensor& w2d,
                                       std::vector<long> dils,
@@ -1198,7 +1056,7 @@ at::Tensor fedkit_conv2d_dilated_bank(const at::Tensor& x,
               "bank weight must be [64, n*R*R*C] contiguous");
   int n = (int)dils.size();
   TORCH_CHECK(n >= 1 && n <= 8 && (int)pads.size() == n, "1..8 taps");
-  int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  int N = x.size(0), C = x.size(1), H = x.size(2);
   TORCH_CHECK(C % 8 == 0, "bank needs C % 8 == 0");
   int kg_per = (int)(R * R * C);
   TORCH_CHECK(kg_per % BK == 0, "bank needs R*R*C % 64 == 0 per tap");
@@ -1217,31 +1075,19 @@ at::Tensor fedkit_conv2d_dilated_bank(const at::Tensor& x,
     TORCH_CHECK(P < 0 || Pt == P, "bank taps disagree on output size");
     P = Pt;
   }
-  at::Tensor xp = shared_pad > 0
-      ? pad_nhwc(x, shared_pad, shared_pad, shared_pad, shared_pad) : x;
+  at::Tensor xp = pad_nhwc(x, shared_pad);
   int Hp = xp.size(2), Wp = xp.size(3);
   long long M = (long long)N * P * P;
   auto y = at::empty({N, ktrue, P, P},
                      x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  bool bm64 = ((M + 127) / 128) < 256;
   int Kg = n * kg_per;
-  auto stream = fedkit_stream();
-  dim3 grid((unsigned)((M + (bm64 ? 63 : 127)) / (bm64 ? 64 : 128)), 1);
-  auto LB = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
-                       (const bf16*)xp.data_ptr(),
-                       (const bf16*)w2d.data_ptr(), (bf16*)y.data_ptr(),
-                       N, Hp, Wp, C, 64, (int)R, (int)R, P, P, Kg, 1,
-                       (int)ktrue, (float*)nullptr, td, VPadDesc{});
-  };
-  if (stride == 1)
-    bm64 ? LB(conv_fwd_kernel<64, 1, 0, 3, true>)
-         : LB(conv_fwd_kernel<128, 1, 0, 3, true>);
-  else
-    bm64 ? LB(conv_fwd_kernel<64, 2, 0, 3, true>)
-         : LB(conv_fwd_kernel<128, 2, 0, 3, true>);
+  const ConvPlan p = plan_conv(M, 64, Kg, (int)stride, ktrue == 64, false, 0,
+                               kBank);
+  launch_conv(p, {N, Hp, Wp, C, 64, (int)R, (int)R, P, P, Kg, 1, (int)ktrue},
+              xp, w2d, y, nullptr, td, VPadDesc{});
   return y;
 }
+
 
 at::Tensor fedkit_conv_small_fwd(const at::Tensor& x, const at::Tensor& w,
                                  long stride, long padding);  // conv_small.hip
@@ -1258,8 +1104,7 @@ at::Tensor fedkit_dilate_pad(const at::Tensor& x, long pt, long pb, long pl,
 at::Tensor fedkit_conv2d_pad_input(const at::Tensor& x, long padding) {
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast),
               "pad_input expects channels_last");
-  if (padding == 0) return x;
-  return pad_nhwc(x, padding, padding, padding, padding);
+  return pad_nhwc(x, (int)padding);
 }
 
 // forward on a PRE-PADDED input (the autograd wrapper saves xp so backward
@@ -1275,8 +1120,7 @@ at::Tensor fedkit_conv2d_fwd_prepadded(const at::Tensor& xp,
   int Reff = (R - 1) * (int)dil + 1, Seff = (S - 1) * (int)dil + 1;
   int P = (Hp - Reff) / (int)stride + 1;
   int Q = (Wp - Seff) / (int)stride + 1;
-  return conv_core(xp, w, (int)stride, P, Q, (int)dil, (int)ktrue,
-                   nullptr, nullptr, 512);
+  return conv_core(xp, w, (int)stride, P, Q, kFwd, (int)dil, (int)ktrue);
 }
 
 // prepadded forward that ALSO emits the BatchNorm stage-1 partials
@@ -1291,10 +1135,9 @@ std::vector<at::Tensor> fedkit_conv2d_fwd_prepadded_bnstats(
   int R = w.size(2), S = w.size(3);
   int P = (Hp - R) / (int)stride + 1;
   int Q = (Wp - S) / (int)stride + 1;
-  // conv_core picks the tile size and sizes the slab to the grid it
-  // launches (no second copy of the tile rule here)
+  // conv_core sizes the slab to the grid its plan launches
   at::Tensor part;
-  auto y = conv_core(xp, w, (int)stride, P, Q, 1, -1, &part, nullptr, 512);
+  auto y = conv_core(xp, w, (int)stride, P, Q, kFwd, 1, -1, &part);
   return {y, part};
 }
 
@@ -1312,10 +1155,8 @@ at::Tensor fedkit_conv2d_fwd(const at::Tensor& x, const at::Tensor& w,
   int Reff = (R - 1) * (int)dil + 1;
   int P = (H + 2 * (int)padding - Reff) / (int)stride + 1;
   int Q = (W + 2 * (int)padding - Reff) / (int)stride + 1;
-  at::Tensor xp = padding > 0 ? pad_nhwc(x, padding, padding, padding, padding)
-                              : x;
-  return conv_core(xp, w, (int)stride, P, Q, (int)dil, (int)ktrue,
-                   nullptr, nullptr, 512);
+  at::Tensor xp = pad_nhwc(x, (int)padding);
+  return conv_core(xp, w, (int)stride, P, Q, kFwd, (int)dil, (int)ktrue);
 }
 
 // dx = conv_dil(dilate_str(gy), rot180(w)); gy must carry the same
@@ -1356,7 +1197,7 @@ at::Tensor fedkit_conv2d_bwd_data(const at::Tensor& gy, const at::Tensor& w,
     // dense GEMM at the SMALL resolution, then one zero-interleave pass
     // (dx[2p][2q] = sum_k gy[p][q][k] w[k][c]).
     int P = gy.size(2), Q = gy.size(3);
-    auto dxs = conv_core(gy, wrot, 1, P, Q, 1, (int)ctrue);
+    auto dxs = conv_core(gy, wrot, 1, P, Q, kBwd, 1, (int)ctrue);
     int pb = (int)H - ((P - 1) * 2 + 1);
     int pr = (int)W - ((Q - 1) * 2 + 1);
     return dilate_pad_nhwc(dxs, 0, pb, 0, pr, 2);
@@ -1384,12 +1225,12 @@ at::Tensor fedkit_conv2d_bwd_data(const at::Tensor& gy, const at::Tensor& w,
       (stride == 1 || (stride == 2 && H >= 16));
   if (vpad_ok) {
     VPadDesc vp{(int)gy.size(2), (int)gy.size(3), pl, (int)stride};
-    return conv_core(gy, wrot, 1, (int)H, (int)W, (int)dil, (int)ctrue,
+    return conv_core(gy, wrot, 1, (int)H, (int)W, kBwd, (int)dil, (int)ctrue,
                      nullptr, &vp);
   }
   int a = (int)((H + 2 * padding - Reff) % stride);
   at::Tensor gyp = dilate_pad_nhwc(gy, pl, pl + a, pl, pl + a, (int)stride);
-  return conv_core(gyp, wrot, 1, (int)H, (int)W, (int)dil, (int)ctrue);
+  return conv_core(gyp, wrot, 1, (int)H, (int)W, kBwd, (int)dil, (int)ctrue);
 }
 
 // bwd-weight from the PRE-PADDED input saved by the forward
@@ -1398,31 +1239,21 @@ at::Tensor fedkit_conv2d_bwd_weight_prepadded(const at::Tensor& gy,
                                               long stride, long R_in,
                                               long S_in, long dil) {
   check_conv_inputs(gy, xp);
-  int N = xp.size(0), C = xp.size(1);
+  int N = xp.size(0), C = xp.size(1), Hp = xp.size(2), Wp = xp.size(3);
   int K = gy.size(1), P = gy.size(2), Q = gy.size(3);
   int R = (int)R_in, S = (int)S_in;
   long long M = (long long)N * P * Q;
   long long RSC = (long long)R * S * C;
+  const DwPlan d = plan_dw(N, C, Hp, Wp, K, P, Q, R, S, (int)stride, (int)dil);
 
   // transpose-then-implicit-GEMM MFMA path (no col buffer, no library GEMM):
-  // see the dw block comment above conv kernels.  Q >= 8 so an m-chunk
-  // stays within one q row.  Stride 1 uses one transposed plane; stride 2
-  // uses EVEN/ODD-column planes (each filter column's parity is fixed, so
-  // 8 consecutive q remain contiguous in its plane) — together 15/17
-  // ResNet18 convs.
-  int Hp = xp.size(2), Wp = xp.size(3);
-  long long NHW = (long long)N * Hp * Wp;
-  bool pow2 = P > 0 && Q > 0 && (P & (P - 1)) == 0 && (Q & (Q - 1)) == 0;
-  // Q==4 via two-piece register staging MEASURED SLOWER than the im2col
-  // + rocBLAS split-K path it would replace (layer4 dw 36 -> 67 us,
-  // C256-s2 30 -> 44): at M = 2048 the library's tiling wins; the
-  // kernel-side QH support stays for reference, disabled here.
-  bool qh = false;
-  bool common = dil == 1 && pow2 && (Q % 8 == 0 || qh) && K % 64 == 0 &&
-      RSC % 64 == 0 && C % 64 == 0 && M % 64 == 0;
-  if ((stride == 1 && common && NHW % 64 == 0) ||
-      (stride == 2 && common && Wp % 2 == 0 && (NHW / 2) % 64 == 0)) {
+  // see the dw block comment above the kernels.  Stride 1 uses one
+  // transposed plane; stride 2 uses EVEN/ODD-column planes (each filter
+  // column's parity is fixed, so 8 consecutive q remain contiguous in its
+  // plane) — together 15/17 ResNet18 convs.
+  if (d.fast) {
     auto stream = fedkit_stream();
+    long long NHW = (long long)N * Hp * Wp;
     auto dyT = at::empty({(long long)K, M}, gy.options());
     at::Tensor xpT, xpT2;
     int Wlane = Wp;
@@ -1455,159 +1286,38 @@ at::Tensor fedkit_conv2d_bwd_weight_prepadded(const at::Tensor& gy,
                        dim3(256), 0, stream, jd, jx, jx2, njobs, tiles);
     int qshift = __builtin_ctz((unsigned)Q);
     int pshift = qshift + __builtin_ctz((unsigned)P);
-    int BMK = K % 128 == 0 ? 128 : 64;     // kout tile (128 ~1.7x faster)
-    // K=64 caps the kout tile; widen the rsc tile instead (NT=2)
-    bool nt2 = BMK == 64 && stride == 1 && RSC >= 128 && !qh;
-    int rsc_tiles = nt2 ? (int)((RSC + 127) / 128) : (int)(RSC / 64);
-    long long mtiles = M / 64;
-    long long tiles_xy = (long long)rsc_tiles * (K / BMK);
-    int maxsplit = nt2 ? 128 : 64;
-    int splits = 1;
-    while (splits < maxsplit && tiles_xy * splits < 512 &&
-           (long long)splits * 2 <= mtiles)
-      splits *= 2;
-    int mps = (int)((mtiles + splits - 1) / splits);
-    auto part = at::empty({splits, (long long)K, RSC},
+    auto part = at::empty({d.splits, (long long)K, RSC},
                           xp.options().dtype(at::kFloat));
     auto dw = at::empty({K, C, R, S},
                         xp.options().memory_format(at::MemoryFormat::ChannelsLast));
-    static const int bglds = []() {
-      const char* e = getenv("FEDKIT_DW_GLDSB");
-      return e ? atoi(e) : 1;
-    }();
-    dim3 grid((unsigned)rsc_tiles, K / BMK, splits);
-    auto LD = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
-                         (const bf16*)dyT.data_ptr(),
-                         (const bf16*)xpT.data_ptr(),
-                         stride == 2 ? (const bf16*)xpT2.data_ptr() : nullptr,
-                         part.data_ptr<float>(),
-                         K, C, N, Hp, Wlane, S, M, (int)RSC, mps,
-                         qshift, Q - 1, pshift, P - 1, PlaneSet{});
-    };
-    if (qh) {
-      // Q == 4 shapes take the two-piece register commit (see kernel doc)
-      if (stride == 2)
-        BMK == 128 ? LD(dw_gemm_kernel<128, 0, 2, 1, 1>)
-                   : LD(dw_gemm_kernel<64, 0, 2, 1, 1>);
-      else
-        BMK == 128 ? LD(dw_gemm_kernel<128, 0, 1, 1, 1>)
-                   : LD(dw_gemm_kernel<64, 0, 1, 1, 1>);
-    } else if (stride == 2) {
-      if (bglds)
-        BMK == 128 ? LD(dw_gemm_kernel<128, 1, 2>)
-                   : LD(dw_gemm_kernel<64, 1, 2>);
-      else
-        BMK == 128 ? LD(dw_gemm_kernel<128, 0, 2>)
-                   : LD(dw_gemm_kernel<64, 0, 2>);
-    } else if (nt2) {
-      bglds ? LD(dw_gemm_kernel<64, 1, 1, 2>)
-            : LD(dw_gemm_kernel<64, 0, 1, 2>);
-    } else if (bglds) {
-      BMK == 128 ? LD(dw_gemm_kernel<128, 1, 1>)
-                 : LD(dw_gemm_kernel<64, 1, 1>);
-    } else {
-      BMK == 128 ? LD(dw_gemm_kernel<128, 0, 1>)
-                 : LD(dw_gemm_kernel<64, 0, 1>);
-    }
+    DwKernel kern = nullptr;
+    for (const DwVariant& v : kDwVariants)
+      if (v.BMK == d.BMK && v.stride == d.stride && v.NT == d.NT)
+        kern = v.kern;
+    TORCH_CHECK(kern, "no dw_gemm_kernel for plan BMK=", d.BMK, " stride=",
+                d.stride, " NT=", d.NT);
+    hipLaunchKernelGGL(kern, dim3(d.rsc_tiles, d.grid_y, d.splits), dim3(256),
+                       0, stream, (const bf16*)dyT.data_ptr(),
+                       (const bf16*)xpT.data_ptr(),
+                       stride == 2 ? (const bf16*)xpT2.data_ptr() : nullptr,
+                       part.data_ptr<float>(), K, C, N, Hp, Wlane, S, M,
+                       (int)RSC, d.mtiles_per_split, qshift, Q - 1, pshift,
+                       P - 1);
     long long L = (long long)K * RSC;
-    if (splits > 8) {
+    if (d.two_stage) {
       auto part2 = at::empty({8, L}, xp.options().dtype(at::kFloat));
       hipLaunchKernelGGL(colsum_stage_kernel,
                          dim3(grid_1d(L, 256, 512), 8), dim3(256), 0, stream,
-                         part.data_ptr<float>(), splits / 8, L,
+                         part.data_ptr<float>(), d.splits / 8, L,
                          part2.data_ptr<float>());
       hipLaunchKernelGGL(colsum_to_bf16_kernel, dim3(grid_1d(L, 256)),
                          dim3(256), 0, stream, part2.data_ptr<float>(), 8, L,
                          (bf16*)dw.data_ptr());
     } else {
       hipLaunchKernelGGL(colsum_to_bf16_kernel, dim3(grid_1d(L, 256)),
-                         dim3(256), 0, stream, part.data_ptr<float>(), splits,
-                         L, (bf16*)dw.data_ptr());
+                         dim3(256), 0, stream, part.data_ptr<float>(),
+                         d.splits, L, (bf16*)dw.data_ptr());
     }
-    return dw;
-  }
-
-  // ---- packed-Q plane path (layer4-class shapes, Q == 4): per-
-  // (filter-column[, h-parity]) transposed planes of width exactly Q make
-  // an 8-m chunk 16 contiguous bytes, so the same glds-staged MFMA dw
-  // GEMM applies.  MEASURED SLOWER than the im2col + rocBLAS split-K path
-  // it would replace (layer4 s1 44.9 vs 40.3 us, s2-C256 45.3 vs 34.0,
-  // gpurun_out/ab_*.log): at M = 2048 the extra plane transposes plus an
-  // underfilled 288-wg GEMM grid lose to the library's tiling — same
-  // conclusion as round 1's two-piece register variant (67 us).  Kept
-  // opt-in (FEDKIT_QP=1) as the measured ledger entry.
-  static const bool use_qp = []() {
-    const char* e = getenv("FEDKIT_QP");
-    return e && atoi(e) == 1;
-  }();
-  bool qp_ok = use_qp && dil == 1 && pow2 && Q == 4 && (P % 2) == 0 &&
-      K % 64 == 0 && RSC % 64 == 0 && C % 64 == 0 && M % 64 == 0 &&
-      (stride == 1 || (stride == 2 && Hp % 2 == 0)) && S <= 3;
-  if (qp_ok) {
-    auto stream = fedkit_stream();
-    auto dyT = at::empty({(long long)K, M}, gy.options());
-    hipLaunchKernelGGL(transpose_mk_kernel, dim3((unsigned)(M / 64), K / 64),
-                       dim3(256), 0, stream, (const bf16*)gy.data_ptr(),
-                       (bf16*)dyT.data_ptr(), M, K, 1LL, 0LL);
-    int Hpl = stride == 1 ? Hp : Hp / 2;
-    long long Mp = (long long)N * Hpl * 4;
-    int nplanes = stride == 1 ? S : 2 * S;
-    TORCH_CHECK(Mp % 64 == 0, "packed-Q plane Mp % 64");
-    auto planes = at::empty({nplanes, (long long)C, Mp}, xp.options());
-    PlaneSet ps = {};
-    for (int t = 0; t < nplanes; ++t) {
-      long long rowstride, rowoff;
-      int cs;
-      if (stride == 1) {                   // plane t = filter column s
-        rowstride = Wp;
-        rowoff = t;
-        cs = 1;
-      } else {                             // plane t = (s, rpar)
-        int s = t / 2, rpar = t % 2;
-        rowstride = 2LL * Wp;
-        rowoff = (long long)rpar * Wp + s;
-        cs = 2;
-      }
-      bf16* outp = (bf16*)planes.data_ptr() + (long long)t * C * Mp;
-      hipLaunchKernelGGL(transpose_pack_kernel,
-                         dim3((unsigned)(Mp / 64), C / 64), dim3(256), 0,
-                         stream, (const bf16*)xp.data_ptr(), outp, Mp, C,
-                         rowstride, rowoff, cs);
-      ps.p[t] = outp;
-    }
-    int BMK = K % 128 == 0 ? 128 : 64;
-    int rsc_tiles = (int)(RSC / 64);
-    long long mtiles = M / 64;
-    long long tiles_xy = (long long)rsc_tiles * (K / BMK);
-    int splits = 1;
-    while (splits < 64 && tiles_xy * splits < 512 &&
-           (long long)splits * 2 <= mtiles)
-      splits *= 2;
-    int mps = (int)((mtiles + splits - 1) / splits);
-    auto part = at::empty({splits, (long long)K, RSC},
-                          xp.options().dtype(at::kFloat));
-    auto dw = at::empty({K, C, R, S},
-                        xp.options().memory_format(at::MemoryFormat::ChannelsLast));
-    int qshift = 2, pshift = 2 + __builtin_ctz((unsigned)P);
-    dim3 grid((unsigned)rsc_tiles, K / BMK, splits);
-    auto LQ = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
-                         (const bf16*)dyT.data_ptr(), (const bf16*)nullptr,
-                         (const bf16*)nullptr, part.data_ptr<float>(),
-                         K, C, N, Hpl, 4, S, M, (int)RSC, mps,
-                         qshift, 3, pshift, P - 1, ps);
-    };
-    if (stride == 1)
-      BMK == 128 ? LQ(dw_gemm_kernel<128, 1, 1, 1, 0, 1>)
-                 : LQ(dw_gemm_kernel<64, 1, 1, 1, 0, 1>);
-    else
-      BMK == 128 ? LQ(dw_gemm_kernel<128, 1, 1, 1, 0, 2>)
-                 : LQ(dw_gemm_kernel<64, 1, 1, 1, 0, 2>);
-    long long L = (long long)K * RSC;
-    hipLaunchKernelGGL(colsum_to_bf16_kernel, dim3(grid_1d(L, 256)),
-                       dim3(256), 0, stream, part.data_ptr<float>(), splits,
-                       L, (bf16*)dw.data_ptr());
     return dw;
   }
 
@@ -1637,14 +1347,11 @@ at::Tensor fedkit_conv2d_bwd_weight_prepadded(const at::Tensor& gy,
   // shape, so split it ourselves: batch the reduction dim into chunks, bmm
   // into fp32 partials, sum — a plain library GEMM per chunk.
   auto dy2d = gy.permute({0, 2, 3, 1}).reshape({M, K});
-  long long Kg2 = (long long)R * S * C;
-  int chunks = 1;
-  while (chunks < 64 && (M / (chunks * 2)) >= 2048 && M % (chunks * 2) == 0)
-    chunks *= 2;
+  const int chunks = d.chunks;
   at::Tensor dw;
   if (chunks > 1) {
     auto dyb = dy2d.reshape({chunks, M / chunks, K});
-    auto colb = col.reshape({chunks, M / chunks, Kg2});
+    auto colb = col.reshape({chunks, M / chunks, RSC});
     auto partial = at::bmm(dyb.transpose(1, 2), colb);  // [chunks, K, Kg2]
     dw = partial.sum(0, false, at::kFloat).to(at::kBFloat16);
   } else {
@@ -1657,7 +1364,6 @@ at::Tensor fedkit_conv2d_bwd_weight_prepadded(const at::Tensor& gy,
 at::Tensor fedkit_conv2d_bwd_weight(const at::Tensor& gy, const at::Tensor& x,
                                     long stride, long padding, long R_in,
                                     long S_in, long dil) {
-  at::Tensor xp = padding > 0 ? pad_nhwc(x, padding, padding, padding, padding)
-                              : x;
+  at::Tensor xp = pad_nhwc(x, (int)padding);
   return fedkit_conv2d_bwd_weight_prepadded(gy, xp, stride, R_in, S_in, dil);
 }

@@ -5,6 +5,8 @@
 #include <torch/extension.h>
 #include <vector>
 
+#include "conv_plan.h"
+
 at::Tensor fedkit_elu_fwd(const at::Tensor& x);
 std::vector<at::Tensor> fedkit_max_pool2d_fwd(const at::Tensor& x, long k);
 at::Tensor fedkit_max_pool2d_bwd(const at::Tensor& gy, const at::Tensor& idx,
@@ -86,6 +88,9 @@ at::Tensor fedkit_conv2d_bwd_data(const at::Tensor& gy, const at::Tensor& w,
 at::Tensor fedkit_conv2d_bwd_weight(const at::Tensor& gy, const at::Tensor& x,
                                     long stride, long padding, long R, long S,
                                     long dil);
+
+std::vector<std::vector<long>> fedkit_conv_variants();
+std::vector<std::vector<long>> fedkit_dw_variants();
 
 void fedkit_adam_step(std::vector<at::Tensor> params,
                       std::vector<at::Tensor> grads,
@@ -211,6 +216,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_bwd_weight", &fedkit_conv2d_bwd_weight, "conv bwd-weight",
         py::arg("gy"), py::arg("x"), py::arg("stride"), py::arg("padding"),
         py::arg("R"), py::arg("S"), py::arg("dil") = 1);
+  // launch planning (csrc/conv_plan.h): pure integer rules, no GPU needed
+  m.def("conv_plan",
+        [](long M, long Kout, long Kg, long stride, bool dense, bool bnpart,
+           long vpad, long caller) {
+          auto p = fedkit_plan::plan_conv(
+              M, (int)Kout, (int)Kg, (int)stride, dense, bnpart, (int)vpad,
+              (fedkit_plan::ConvCaller)caller);
+          return py::make_tuple(p.BM, p.stride, p.mode, p.stages, p.vpad,
+                                p.multitap, p.grid_x, p.grid_y, p.splits);
+        },
+        "conv launch plan: (BM, stride, mode, stages, vpad, multitap, "
+        "grid_x, grid_y, splits); caller 0 forward, 1 backward, 2 bank",
+        py::arg("M"), py::arg("Kout"), py::arg("Kg"), py::arg("stride"),
+        py::arg("dense"), py::arg("bnpart"), py::arg("vpad"),
+        py::arg("caller"));
+  m.def("dw_plan",
+        [](long N, long C, long Hp, long Wp, long K, long P, long Q, long R,
+           long S, long stride, long dil) {
+          auto d = fedkit_plan::plan_dw((int)N, (int)C, (int)Hp, (int)Wp,
+                                        (int)K, (int)P, (int)Q, (int)R,
+                                        (int)S, (int)stride, (int)dil);
+          return py::make_tuple(d.fast, d.BMK, d.NT, d.stride, d.rsc_tiles,
+                                d.grid_y, d.splits, d.mtiles_per_split,
+                                d.two_stage, d.chunks);
+        },
+        "bwd-weight plan: (fast, BMK, NT, stride, rsc_tiles, grid_y, splits, "
+        "mtiles_per_split, two_stage, chunks)",
+        py::arg("N"), py::arg("C"), py::arg("Hp"), py::arg("Wp"),
+        py::arg("K"), py::arg("P"), py::arg("Q"), py::arg("R"), py::arg("S"),
+        py::arg("stride"), py::arg("dil") = 1);
+  m.def("conv_variants", &fedkit_conv_variants,
+        "instantiated conv_fwd_kernel variants from the dispatch table: "
+        "[BM, stride, mode, stages, vpad, multitap]");
+  m.def("dw_variants", &fedkit_dw_variants,
+        "instantiated dw_gemm_kernel variants: [BMK, stride, NT]");
   m.def("adam_step", &fedkit_adam_step,
         "fused Adam: one kernel updates every parameter (fp32 master)");
   m.def("welford_update", &fedkit_welford_update,

@@ -22,6 +22,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_menus import BN_CONV_CASES
+
 pytestmark = pytest.mark.gpu
 
 EPS = 1e-5
@@ -454,17 +456,9 @@ def test_variance_conditioning(mu):
 
 # ------------------------------------------- 6. conv-epilogue BN statistics
 
-# (xp shape, Kout, R, stride); M and the tile regime of each row are in
-# profiles/bn_numerics.md.  "window" = ceil(M/128) * Kout/64 in [256, 512),
-# where the conv launches 64-row tiles.
-CONV_CASES = [
-    ((2, 64, 11, 11), 128, 3, 1),     # BM64, M tail 34, two column blocks
-    ((2, 64, 19, 19), 64, 3, 2),      # stride 2
-    ((3, 64, 9, 9), 64, 1, 2),        # 1x1 projection
-    ((4, 8, 35, 35), 512, 3, 1),      # window, M tail 4, Kg = 72 tail tile
-    ((32, 64, 34, 34), 64, 3, 1),     # window, ResNet layer1 at batch 32
-    ((8, 8, 35, 35), 512, 3, 1),      # BM128, M tail 8
-]
+# (xp shape, Kout, R, stride): the menu lives in tests/conv_menus.py, shared
+# with the CPU planner test.
+CONV_CASES = BN_CONV_CASES
 WINDOW = {CONV_CASES[3], CONV_CASES[4]}
 
 

@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_menus import BANK_CASES, GEN_N, RESNET_SHAPES, VAE_CPC_CONVS
+
 pytestmark = pytest.mark.gpu
 
 
@@ -213,27 +215,8 @@ def test_bn_eval_mode():
 
 # ----------------------------------------------------------------------- conv
 
-RESNET_SHAPES = [
-    # (N, C, H, K, R, stride) — the ResNet18 CIFAR conv menu
-    (16, 64, 32, 64, 3, 1),
-    (16, 64, 32, 128, 3, 2),
-    (16, 128, 16, 128, 3, 1),
-    (16, 128, 16, 256, 3, 2),
-    (16, 256, 8, 256, 3, 1),
-    (16, 256, 8, 512, 3, 2),
-    (16, 512, 4, 512, 3, 1),
-    (16, 64, 32, 128, 1, 2),   # shortcut projections
-    # N=64 so the stride-2 even/odd-plane dw fast path qualifies
-    # ((N*Hp*Wp/2) % 64 == 0 — N=16 falls back to the library path)
-    (64, 64, 32, 128, 3, 2),
-    (64, 128, 16, 256, 3, 2),
-    (16, 128, 16, 256, 1, 2),
-    (16, 256, 8, 512, 1, 2),
-    # bench-size layer4 shapes: the packed-Q (Q=4) dw plane path
-    (128, 512, 4, 512, 3, 1),
-    (128, 256, 8, 512, 3, 2),
-]
-
+# shape menus: tests/conv_menus.py (shared with the CPU planner test, which
+# checks that they reach every instantiated conv kernel)
 
 @pytest.mark.parametrize("N,C,H,K,R,stride", RESNET_SHAPES)
 def test_conv_fwd_vs_torch(N, C, H, K, R, stride):
@@ -356,28 +339,11 @@ def test_resnet18_training_step_bf16():
 
 # ------------------------------------------------------- generic conv (VAE/CPC)
 
-VAE_CPC_CONVS = [
-    # (Cin, Kout, H, ksize, stride, pad, dil) — VAE encoder 4x4-s2 chain
-    # (simple_models.py:249-255) and the CPC dilated bank / 2x2 / 1x1 convs
-    # (simple_models.py:441-460, 478-481, 503-504)
-    (3, 12, 32, 4, 2, 1, 1),
-    (12, 24, 16, 4, 2, 1, 1),
-    (24, 48, 8, 4, 2, 1, 1),
-    (48, 96, 4, 4, 2, 1, 1),
-    (8, 8, 32, 4, 2, 3, 2),      # CPC dilated bank d=2
-    (8, 8, 32, 4, 2, 6, 4),      # d=4
-    (8, 8, 32, 4, 2, 24, 16),    # d=16
-    (40, 256, 16, 4, 2, 1, 1),   # CPC conv2 (8*5 -> latent/4)
-    (256, 256, 6, 2, 1, 1, 1),   # CPC contextgen 2x2 pad 1
-    (1024, 256, 4, 1, 1, 0, 1),  # CPC predictor 1x1
-]
-
-
 @pytest.mark.parametrize("Cin,Kout,H,ks,stride,pad,dil", VAE_CPC_CONVS)
 def test_gen_conv_fwd_bwd_vs_torch(Cin, Kout, H, ks, stride, pad, dil):
     from fedkit.ops.conv import _gen_conv
     torch.manual_seed(11)
-    N = 16
+    N = GEN_N
     x = (torch.randn(N, Cin, H, H, device="cuda") * 0.5).requires_grad_(True)
     w = (torch.randn(Kout, Cin, ks, ks, device="cuda") * 0.1).requires_grad_(True)
     b = torch.randn(Kout, device="cuda", requires_grad=True)
@@ -915,6 +881,30 @@ def test_dilated_bank_fused_vs_per_conv():
     for t, m in enumerate(mods):
         assert frob_err(gws[t], m.weight.grad) < 3e-2, t
         assert frob_err(gbs[t], m.bias.grad) < 3e-2, t
+
+
+@pytest.mark.parametrize("N,C,H,R,stride,kt,dils,pads", BANK_CASES)
+def test_dilated_bank_kernel_variants(N, C, H, R, stride, kt, dils, pads):
+    """conv2d_dilated_bank called directly at shapes that reach each of its
+    four kernels (64/128-row tile x stride 1/2) vs the per-tap fp32 convs;
+    same bound as the fused-bank forward check above."""
+    ext = _ext()
+    torch.manual_seed(18)
+    x = torch.randn(N, C, H, H, device="cuda", dtype=torch.bfloat16)
+    ws = [torch.randn(kt, C, R, R, device="cuda", dtype=torch.bfloat16) * 0.1
+          for _ in dils]
+    kg = R * R * C
+    w2d = torch.zeros(64, kg * len(dils), device="cuda", dtype=torch.bfloat16)
+    for t, w in enumerate(ws):
+        w2d[t * kt:(t + 1) * kt, t * kg:(t + 1) * kg] = \
+            w.permute(0, 2, 3, 1).reshape(kt, kg)
+    y = ext.conv2d_dilated_bank(
+        x.contiguous(memory_format=torch.channels_last), w2d, list(dils),
+        list(pads), stride, R, kt * len(dils))
+    want = torch.cat([F.conv2d(x.float(), w.float(), None, stride, p, d)
+                      for w, d, p in zip(ws, dils, pads)], dim=1)
+    assert y.shape == want.shape
+    assert frob_err(y, want) < 2e-2, frob_err(y, want)
 
 
 def test_encoder_bank_path_uses_fusion():

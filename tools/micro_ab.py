@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""A/B microbench for the env-gated conv paths (vpad bwd-data, packed-Q dw).
+"""A/B microbench for the env-gated virtual-pad bwd-data path, plus the
+linear and layer4-class bwd-weight timings it is usually read next to.
 
-The gates are read once per process (static), so run this twice:
-    python tools/micro_ab.py                      # new paths
-    FEDKIT_NO_VPAD=1 python tools/micro_ab.py   # old paths (FEDKIT_QP=1 enables packed-Q dw)
+The gate is read once per process (static), so run this twice:
+    python tools/micro_ab.py                    # virtual pad
+    FEDKIT_NO_VPAD=1 python tools/micro_ab.py   # materialized dilate+pad
 Prints one line per shape: op, shape, mean us.
 """
 
@@ -62,7 +63,7 @@ def main():
         x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
         us = timeit(lambda: ext.linear_bwd_weight(gy, x, True))
         print(f"{tag} linear_dw M{M} K{K} N{N}: {us:8.1f} us")
-    # layer4-class dw shapes (packed-Q)
+    # layer4-class dw shapes (Q == 4: library path)
     for C, H, K, stride in [(512, 4, 512, 1), (256, 8, 512, 2)]:
         P = H // stride
         x = torch.randn(BATCH, C, H, H, device="cuda",
@@ -78,29 +79,3 @@ def main():
 if __name__ == "__main__":
     main()
 
-
-def fwd_sweep():
-    """Forward conv timings per flagship shape (run under env combos:
-    FEDKIT_CONV_STAGES=2, FEDKIT_CONV_BM64=1)."""
-    tag = []
-    if os.environ.get("FEDKIT_CONV_BM64") == "1":
-        tag.append("bm64")
-    if os.environ.get("FEDKIT_CONV_STAGES") == "2":
-        tag.append("st2")
-    tag = "+".join(tag) or "default"
-    for C, H, K, stride in [(64, 32, 64, 1), (128, 16, 128, 1),
-                            (256, 8, 256, 1), (512, 4, 512, 1),
-                            (64, 32, 128, 2), (128, 16, 256, 2),
-                            (256, 8, 512, 2)]:
-        x = torch.randn(BATCH, C, H, H, device="cuda",
-                        dtype=torch.bfloat16).contiguous(
-            memory_format=torch.channels_last)
-        w = (torch.randn(K, C, 3, 3, device="cuda", dtype=torch.bfloat16)
-             * 0.05).contiguous(memory_format=torch.channels_last)
-        xp = ext.conv2d_pad_input(x, 1)
-        us = timeit(lambda: ext.conv2d_fwd_prepadded(xp, w, stride))
-        print(f"FWD[{tag}] C{C} H{H} K{K} s{stride}: {us:8.1f} us")
-
-
-if os.environ.get("FEDKIT_FWD_SWEEP") == "1":
-    fwd_sweep()
