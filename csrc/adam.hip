@@ -1,5 +1,5 @@
 // Fused Adam step: ONE kernel updates every parameter tensor of the
-// model (descriptor-table form, like flat_ops/cast).  torch's foreach
+// model (segment tables of csrc/multi_tensor.h).  torch's foreach
 // Adam spends ~110 us/step on ResNet18 across ~10 multi-tensor sweeps
 // (lerp/addcmul/sqrt/div chains re-reading m/v each time); the fused
 // form is one pass at the traffic floor:
@@ -9,117 +9,82 @@
 // with bias corrections bc1 = 1-b1^t, bc2 = 1-b2^t computed on host.
 // All fp32 (master weights / grads / state), 4 elems per lane.
 
-#include "fedkit_common.h"
+#include "multi_tensor.h"
 
 namespace {
 
-constexpr int kAdamMax = 48;
+using fedkit_mt::SegTable;
 
-struct AdamDesc {
-  float* p[kAdamMax];
-  const float* g[kAdamMax];
-  float* m[kAdamMax];
-  float* v[kAdamMax];
-  long long offset[kAdamMax + 1];
-  int n;
-};
+// pointer arrays of the table: param, grad, exp_avg, exp_avg_sq
+enum { kP, kG, kM, kV };
 
-__device__ __forceinline__ int adam_find(const AdamDesc& d, long long i) {
-  int lo = 0, hi = d.n - 1;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) >> 1;
-    if (i >= d.offset[mid]) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-__global__ void adam_step_kernel(AdamDesc d, long long total, float lr,
+__global__ void adam_step_kernel(SegTable<4> d, long long total, float lr,
                                  float b1, float b2, float eps,
                                  float inv_bc1, float inv_sqrt_bc2,
                                  float weight_decay) {
+  // Roundings are spelled out (contraction off, explicit fmaf) so they do
+  // not depend on which products the optimizer picks to fuse.  The two paths
+  // round v and the denominator differently, as they always have: fused on
+  // the vector path, separate multiply and add on the per-element path.
+#pragma clang fp contract(off)
   typedef __attribute__((ext_vector_type(4))) float f4;
-  const long long units = (total + 3) >> 2;
-  for (long long u = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       u < units; u += (long long)gridDim.x * blockDim.x) {
-    long long i0 = u << 2;
-    int t = adam_find(d, i0);
-    long long j = i0 - d.offset[t];
-    if (i0 + 4 <= d.offset[t + 1]) {
-      f4 pv, gv, mv, vv;
-      __builtin_memcpy(&pv, d.p[t] + j, 16);
-      __builtin_memcpy(&gv, d.g[t] + j, 16);
-      __builtin_memcpy(&mv, d.m[t] + j, 16);
-      __builtin_memcpy(&vv, d.v[t] + j, 16);
+  fedkit_mt::for_each_unit<4>(
+      d, total,
+      [&](int t, long long j, long long) {
+        f4 pv, gv, mv, vv;
+        __builtin_memcpy(&pv, d.at<float>(kP, t) + j, 16);
+        __builtin_memcpy(&gv, d.at<const float>(kG, t) + j, 16);
+        __builtin_memcpy(&mv, d.at<float>(kM, t) + j, 16);
+        __builtin_memcpy(&vv, d.at<float>(kV, t) + j, 16);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float g = gv[k] + weight_decay * pv[k];
-        float m = b1 * mv[k] + (1.f - b1) * g;
-        float v = b2 * vv[k] + (1.f - b2) * g * g;
-        mv[k] = m;
-        vv[k] = v;
-        pv[k] -= lr * (m * inv_bc1) / (sqrtf(v) * inv_sqrt_bc2 + eps);
-      }
-      __builtin_memcpy(d.p[t] + j, &pv, 16);
-      __builtin_memcpy(d.m[t] + j, &mv, 16);
-      __builtin_memcpy(d.v[t] + j, &vv, 16);
-    } else {
-      for (long long i = i0; i < i0 + 4 && i < total; ++i) {
-        int tt = adam_find(d, i);
-        long long jj = i - d.offset[tt];
-        float g = d.g[tt][jj] + weight_decay * d.p[tt][jj];
-        float m = b1 * d.m[tt][jj] + (1.f - b1) * g;
-        float v = b2 * d.v[tt][jj] + (1.f - b2) * g * g;
-        d.m[tt][jj] = m;
-        d.v[tt][jj] = v;
-        d.p[tt][jj] -= lr * (m * inv_bc1) / (sqrtf(v) * inv_sqrt_bc2 + eps);
-      }
-    }
-  }
+        for (int k = 0; k < 4; ++k) {
+          float g = fmaf(weight_decay, pv[k], gv[k]);
+          float m = fmaf(b1, mv[k], (1.f - b1) * g);
+          float v = fmaf(b2, vv[k], (1.f - b2) * g * g);
+          mv[k] = m;
+          vv[k] = v;
+          pv[k] -= lr * (m * inv_bc1) / fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+        }
+        __builtin_memcpy(d.at<float>(kP, t) + j, &pv, 16);
+        __builtin_memcpy(d.at<float>(kM, t) + j, &mv, 16);
+        __builtin_memcpy(d.at<float>(kV, t) + j, &vv, 16);
+      },
+      [&](int t, long long j, long long) {
+        float* pp = d.at<float>(kP, t) + j;
+        float* mp = d.at<float>(kM, t) + j;
+        float* vp = d.at<float>(kV, t) + j;
+        float g = fmaf(weight_decay, *pp, d.at<const float>(kG, t)[j]);
+        float m = fmaf(b1, *mp, (1.f - b1) * g);
+        float v = b2 * *vp + (1.f - b2) * g * g;
+        *mp = m;
+        *vp = v;
+        *pp -= lr * (m * inv_bc1) / (sqrtf(v) * inv_sqrt_bc2 + eps);
+      });
 }
 
 }  // namespace
 
-// params/grads/exp_avg/exp_avg_sq: parallel lists (<= 48 per call; the
-// caller chunks).  step is the POST-increment step count (torch Adam
-// semantics: state['step'] += 1 before use).
+// params/grads/exp_avg/exp_avg_sq: parallel lists of any length; every
+// tensor is validated before the first launch, then one launch per 48.
+// step is the POST-increment step count (torch Adam semantics:
+// state['step'] += 1 before use).
 void fedkit_adam_step(std::vector<at::Tensor> params,
                       std::vector<at::Tensor> grads,
                       std::vector<at::Tensor> exp_avg,
                       std::vector<at::Tensor> exp_avg_sq, double lr,
                       double beta1, double beta2, double eps, long step,
                       double weight_decay) {
-  TORCH_CHECK(params.size() == grads.size() &&
-              params.size() == exp_avg.size() &&
-              params.size() == exp_avg_sq.size(), "adam: list mismatch");
+  auto cs = fedkit_mt::build_chunks<4>(
+      "adam_step", {&params, &grads, &exp_avg, &exp_avg_sq},
+      {at::kFloat, at::kFloat, at::kFloat, at::kFloat});
+  const fedkit_mt::DeviceGuard guard(params[0].device());
   double bc1 = 1.0 - std::pow(beta1, (double)step);
   double bc2 = 1.0 - std::pow(beta2, (double)step);
   auto stream = fedkit_stream();
-  size_t idx = 0;
-  while (idx < params.size()) {
-    AdamDesc d;
-    d.n = 0;
-    long long off = 0;
-    while (idx < params.size() && d.n < kAdamMax) {
-      TORCH_CHECK(params[idx].scalar_type() == at::kFloat &&
-                  grads[idx].scalar_type() == at::kFloat,
-                  "fused adam is fp32-only");
-      TORCH_CHECK(params[idx].is_non_overlapping_and_dense() &&
-                  grads[idx].is_non_overlapping_and_dense(),
-                  "fused adam needs dense tensors");
-      d.p[d.n] = params[idx].data_ptr<float>();
-      d.g[d.n] = grads[idx].data_ptr<float>();
-      d.m[d.n] = exp_avg[idx].data_ptr<float>();
-      d.v[d.n] = exp_avg_sq[idx].data_ptr<float>();
-      d.offset[d.n] = off;
-      off += params[idx].numel();
-      ++d.n;
-      ++idx;
-    }
-    d.offset[d.n] = off;
-    if (off == 0) continue;
-    hipLaunchKernelGGL(adam_step_kernel, dim3(grid_1d((off + 3) / 4, 256)),
-                       dim3(256), 0, stream, d, off, (float)lr, (float)beta1,
+  for (const auto& c : cs.chunks)
+    hipLaunchKernelGGL(adam_step_kernel,
+                       dim3(grid_1d((c.total + 3) / 4, 256)), dim3(256), 0,
+                       stream, c.d, c.total, (float)lr, (float)beta1,
                        (float)beta2, (float)eps, (float)(1.0 / bc1),
                        (float)(1.0 / std::sqrt(bc2)), (float)weight_decay);
-  }
 }

@@ -7,8 +7,8 @@
 // over the trainable block x.  As stock torch ops that is a cat of the
 // block, ~10 elementwise/reduction launches forward and the autograd replay
 // backward.  Here the forward is ONE streaming reduction that reads the
-// parameter tensors in place through a by-value descriptor table (<= 48
-// tensors per launch, like pack/unpack in flat_ops.hip) and the
+// parameter tensors in place through by-value segment tables (<= 48
+// tensors per launch, csrc/multi_tensor.h) and the
 // backward is ONE elementwise pass writing the closed-form gradient
 //   go * (y + rho (x-z) + lambda1 sign(x) + 2 lambda2 x)
 // in the same physical (storage) element order the packed z / y use.
@@ -28,35 +28,18 @@
 // otherwise that side falls back to four dword accesses.  Units that
 // straddle a tensor boundary or the tail take a per-element scalar path.
 
-#include "fedkit_common.h"
-
-#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
+#include "multi_tensor.h"
 
 namespace {
 
-// launches and allocations go to the operands' device, not the current one
-using DeviceGuard = c10::hip::OptionalHIPGuardMasqueradingAsCUDA;
+using fedkit_mt::DeviceGuard;
+using fedkit_mt::for_each_unit;
+using fedkit_mt::SegTable;
 
-constexpr int kMaxTensors = 48;
 constexpr int kBlock = 256;
 constexpr int kRedGrid = 512;   // workgroup cap of the reduction kernels
 
 typedef __attribute__((ext_vector_type(4))) float f4;
-
-struct PDesc {
-  const float* src[kMaxTensors];
-  long long offset[kMaxTensors + 1];  // prefix offsets into the chunk's slice
-  int n;
-};
-
-__device__ __forceinline__ int find_tensor(const PDesc& d, long long i) {
-  int lo = 0, hi = d.n - 1;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) >> 1;
-    if (i >= d.offset[mid]) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ bool aligned16(const void* p) {
   return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
@@ -117,33 +100,26 @@ __device__ __forceinline__ float pen_grad(float x, float z, float y,
 // z / y already point at the chunk's slice of the flat vectors.
 template <bool HZ, bool HY>
 __global__ void __launch_bounds__(kBlock)
-penalty_fwd_kernel(PDesc d, const float* __restrict__ z,
+penalty_fwd_kernel(SegTable<1> d, const float* __restrict__ z,
                    const float* __restrict__ y, float hrho, float l1,
                    float l2, long long total, float* __restrict__ part) {
   __shared__ float red[4];
   float acc = 0.f;
-  const long long units = (total + 3) >> 2;
-  for (long long u = blockIdx.x * (long long)kBlock + threadIdx.x; u < units;
-       u += (long long)gridDim.x * kBlock) {
-    long long i0 = u << 2;
-    int t = find_tensor(d, i0);
-    if (i0 + 4 <= d.offset[t + 1]) {
-      f4 xv = load4(d.src[t] + (i0 - d.offset[t]));
-      f4 zv = {}, yv = {};
-      if (HZ) zv = load4(z + i0);
-      if (HY) yv = load4(y + i0);
+  for_each_unit<4>(
+      d, total,
+      [&](int t, long long j, long long i0) {
+        f4 xv = load4(d.at<const float>(0, t) + j);
+        f4 zv = {}, yv = {};
+        if (HZ) zv = load4(z + i0);
+        if (HY) yv = load4(y + i0);
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        acc += pen_term<HZ, HY>(xv[k], zv[k], yv[k], hrho, l1, l2);
-    } else {
-      for (long long i = i0; i < i0 + 4 && i < total; ++i) {
-        int tt = find_tensor(d, i);
-        float x = d.src[tt][i - d.offset[tt]];
-        acc += pen_term<HZ, HY>(x, HZ ? z[i] : 0.f, HY ? y[i] : 0.f, hrho,
-                                l1, l2);
-      }
-    }
-  }
+        for (int k = 0; k < 4; ++k)
+          acc += pen_term<HZ, HY>(xv[k], zv[k], yv[k], hrho, l1, l2);
+      },
+      [&](int t, long long j, long long i) {
+        acc += pen_term<HZ, HY>(d.at<const float>(0, t)[j], HZ ? z[i] : 0.f,
+                                HY ? y[i] : 0.f, hrho, l1, l2);
+      });
   float s = block_sum(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
@@ -152,34 +128,27 @@ penalty_fwd_kernel(PDesc d, const float* __restrict__ z,
 // slice of the flat vectors, go is a device scalar.
 template <bool HZ, bool HY>
 __global__ void __launch_bounds__(kBlock)
-penalty_bwd_kernel(PDesc d, const float* __restrict__ z,
+penalty_bwd_kernel(SegTable<1> d, const float* __restrict__ z,
                    const float* __restrict__ y, float rho, float l1,
                    float l2x2, const float* __restrict__ go_ptr,
                    long long total, float* __restrict__ g) {
   const float go = *go_ptr;
-  const long long units = (total + 3) >> 2;
-  for (long long u = blockIdx.x * (long long)kBlock + threadIdx.x; u < units;
-       u += (long long)gridDim.x * kBlock) {
-    long long i0 = u << 2;
-    int t = find_tensor(d, i0);
-    if (i0 + 4 <= d.offset[t + 1]) {
-      f4 xv = load4(d.src[t] + (i0 - d.offset[t]));
-      f4 zv = {}, yv = {}, gv;
-      if (HZ) zv = load4(z + i0);
-      if (HY) yv = load4(y + i0);
+  for_each_unit<4>(
+      d, total,
+      [&](int t, long long j, long long i0) {
+        f4 xv = load4(d.at<const float>(0, t) + j);
+        f4 zv = {}, yv = {}, gv;
+        if (HZ) zv = load4(z + i0);
+        if (HY) yv = load4(y + i0);
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        gv[k] = pen_grad<HZ, HY>(xv[k], zv[k], yv[k], rho, l1, l2x2, go);
-      store4(g + i0, gv);
-    } else {
-      for (long long i = i0; i < i0 + 4 && i < total; ++i) {
-        int tt = find_tensor(d, i);
-        float x = d.src[tt][i - d.offset[tt]];
-        g[i] = pen_grad<HZ, HY>(x, HZ ? z[i] : 0.f, HY ? y[i] : 0.f, rho, l1,
-                                l2x2, go);
-      }
-    }
-  }
+        for (int k = 0; k < 4; ++k)
+          gv[k] = pen_grad<HZ, HY>(xv[k], zv[k], yv[k], rho, l1, l2x2, go);
+        store4(g + i0, gv);
+      },
+      [&](int t, long long j, long long i) {
+        g[i] = pen_grad<HZ, HY>(d.at<const float>(0, t)[j], HZ ? z[i] : 0.f,
+                                HY ? y[i] : 0.f, rho, l1, l2x2, go);
+      });
 }
 
 // y += rho (x - z);  part[blockIdx.x] = partial sum of (rho (x - z))^2
@@ -255,82 +224,15 @@ bb_stats_kernel(const float* __restrict__ y, const float* __restrict__ yh,
   }
 }
 
-// out[c] = sum_p part[p][c], one wave per column, rows in a fixed order
-__global__ void consensus_finalize_kernel(const float* __restrict__ part,
-                                          int np, int ncol,
-                                          float* __restrict__ out) {
-  int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  int lane = threadIdx.x & 63;
-  if (c >= ncol) return;
-  float s = 0.f;
-  for (int p = lane; p < np; p += 64) s += part[(long long)p * ncol + c];
-#pragma unroll
-  for (int off = 32; off; off >>= 1) s += __shfl_down(s, off, kWave);
-  if (lane == 0) out[c] = s;
-}
-
-void finalize(const at::Tensor& part, int np, int ncol, at::Tensor& out,
-              hipStream_t stream) {
-  hipLaunchKernelGGL(consensus_finalize_kernel, dim3((ncol + 3) / 4),
-                     dim3(256), 0, stream, part.data_ptr<float>(), np, ncol,
-                     out.data_ptr<float>());
-}
-
-// One PDesc per <= 48 tensors; `base` is the chunk's offset into the flat
-// vectors and `total` its element count.
-struct Chunk {
-  PDesc d;
-  long long base, total;
-};
-
-std::vector<Chunk> build_chunks(const std::vector<at::Tensor>& params,
-                                long long* n_out) {
-  std::vector<Chunk> chunks;
-  long long flat_off = 0;
-  size_t idx = 0;
-  while (idx < params.size()) {
-    Chunk c;
-    c.d.n = 0;
-    c.base = flat_off;
-    while (idx < params.size() && c.d.n < kMaxTensors) {
-      const at::Tensor& t = params[idx];
-      TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat,
-                  "consensus penalty: parameters must be fp32 GPU tensors");
-      TORCH_CHECK(t.device() == params[0].device(),
-                  "consensus penalty: parameters on different devices");
-      TORCH_CHECK(t.is_non_overlapping_and_dense(),
-                  "consensus penalty needs dense tensors");
-      c.d.offset[c.d.n] = flat_off - c.base;
-      c.d.src[c.d.n] = (const float*)t.data_ptr();
-      flat_off += t.numel();
-      ++c.d.n;
-      ++idx;
-    }
-    c.d.offset[c.d.n] = flat_off - c.base;
-    c.total = flat_off - c.base;
-    if (c.total > 0) chunks.push_back(c);
-  }
-  *n_out = flat_off;
-  return chunks;
-}
-
 const float* flat_ptr(const c10::optional<at::Tensor>& v, long long n,
                       const at::Tensor& like, const char* name) {
   if (!v.has_value()) return nullptr;
-  TORCH_CHECK(v->scalar_type() == at::kFloat && v->is_contiguous() &&
-              v->numel() == n && v->device() == like.device(),
-              "consensus penalty: ", name,
-              " must be a contiguous fp32 vector of the block's length on "
-              "the parameters' device");
+  fedkit_mt::check_flat("consensus penalty", name, *v, like, n);
   return v->data_ptr<float>();
 }
 
 void check_vec(const at::Tensor& v, const at::Tensor& like, const char* op) {
-  TORCH_CHECK(v.is_cuda() && v.scalar_type() == at::kFloat &&
-              v.is_contiguous() && v.numel() == like.numel() &&
-              v.device() == like.device(),
-              op, ": operands must be contiguous fp32 GPU vectors of one "
-              "length on one device");
+  fedkit_mt::check_flat(op, "every operand", v, like, like.numel());
 }
 
 }  // namespace
@@ -340,11 +242,12 @@ at::Tensor fedkit_penalty_fwd(std::vector<at::Tensor> params,
                               c10::optional<at::Tensor> z,
                               c10::optional<at::Tensor> y, double rho,
                               double lambda1, double lambda2) {
-  TORCH_CHECK(!params.empty(), "consensus penalty: no parameters");
   TORCH_CHECK(z.has_value() || !y.has_value(),
               "consensus penalty: y needs z");
-  long long n = 0;
-  auto chunks = build_chunks(params, &n);
+  const auto cs = fedkit_mt::build_chunks<1>("consensus penalty", {&params},
+                                             {at::kFloat});
+  const auto& chunks = cs.chunks;
+  const long long n = cs.total;
   const DeviceGuard guard(params[0].device());
   const float* zp = flat_ptr(z, n, params[0], "z");
   const float* yp = flat_ptr(y, n, params[0], "y");
@@ -357,7 +260,7 @@ at::Tensor fedkit_penalty_fwd(std::vector<at::Tensor> params,
   const float hrho = 0.5f * (float)rho, l1 = (float)lambda1,
               l2 = (float)lambda2;
   int np = 0;
-  for (const Chunk& c : chunks) {
+  for (const auto& c : chunks) {
     int nb = grid_1d((c.total + 3) >> 2, kBlock, kRedGrid);
     if (yp) {
       hipLaunchKernelGGL((penalty_fwd_kernel<true, true>), dim3(nb),
@@ -376,7 +279,7 @@ at::Tensor fedkit_penalty_fwd(std::vector<at::Tensor> params,
     }
     np += nb;
   }
-  finalize(part, np, 1, out, stream);
+  fedkit_colsum_finalize(pp, np, 1, out.data_ptr<float>(), stream);
   return out.reshape({});
 }
 
@@ -386,15 +289,14 @@ at::Tensor fedkit_penalty_bwd(std::vector<at::Tensor> params,
                               c10::optional<at::Tensor> y, double rho,
                               double lambda1, double lambda2,
                               const at::Tensor& grad_out) {
-  TORCH_CHECK(!params.empty(), "consensus penalty: no parameters");
   TORCH_CHECK(z.has_value() || !y.has_value(),
               "consensus penalty: y needs z");
-  TORCH_CHECK(grad_out.is_cuda() && grad_out.scalar_type() == at::kFloat &&
-              grad_out.numel() == 1 &&
-              grad_out.device() == params[0].device(),
-              "consensus penalty: grad_out must be a device fp32 scalar");
-  long long n = 0;
-  auto chunks = build_chunks(params, &n);
+  const auto cs = fedkit_mt::build_chunks<1>("consensus penalty", {&params},
+                                             {at::kFloat});
+  const auto& chunks = cs.chunks;
+  const long long n = cs.total;
+  fedkit_mt::check_flat("consensus penalty", "grad_out", grad_out, params[0],
+                        1);
   const DeviceGuard guard(params[0].device());
   const float* zp = flat_ptr(z, n, params[0], "z");
   const float* yp = flat_ptr(y, n, params[0], "y");
@@ -404,7 +306,7 @@ at::Tensor fedkit_penalty_bwd(std::vector<at::Tensor> params,
   auto stream = fedkit_stream();
   const float r = (float)rho, l1 = (float)lambda1,
               l2x2 = 2.f * (float)lambda2;
-  for (const Chunk& c : chunks) {
+  for (const auto& c : chunks) {
     int nb = grid_1d((c.total + 3) >> 2, kBlock);
     if (yp) {
       hipLaunchKernelGGL((penalty_bwd_kernel<true, true>), dim3(nb),
@@ -442,7 +344,8 @@ at::Tensor fedkit_admm_dual_update(at::Tensor y, const at::Tensor& x,
                      stream, y.data_ptr<float>(), x.data_ptr<float>(),
                      z.data_ptr<float>(), (float)rho, n,
                      part.data_ptr<float>());
-  finalize(part, nb, 1, out, stream);
+  fedkit_colsum_finalize(part.data_ptr<float>(), nb, 1,
+                         out.data_ptr<float>(), stream);
   return out.reshape({});
 }
 
@@ -467,6 +370,7 @@ at::Tensor fedkit_bb_stats(const at::Tensor& y, const at::Tensor& yhat0,
                      y.data_ptr<float>(), yhat0.data_ptr<float>(),
                      x.data_ptr<float>(), z.data_ptr<float>(),
                      x0.data_ptr<float>(), n, part.data_ptr<float>());
-  finalize(part, nb, 6, out, stream);
+  fedkit_colsum_finalize(part.data_ptr<float>(), nb, 6,
+                         out.data_ptr<float>(), stream);
   return out;
 }

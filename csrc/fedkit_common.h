@@ -21,6 +21,11 @@ static inline int grid_1d(long long total, int block, int cap = 2048) {
   return (int)std::min<long long>(g, cap);
 }
 
+// out[c] = sum_r part[r][c] for a row-major [rows][cols] slab of per-workgroup
+// partials, rows summed in a fixed order (flat_ops.hip)
+void fedkit_colsum_finalize(const float* part, int rows, int cols, float* out,
+                            hipStream_t stream);
+
 // dtype tags
 template <typename T> struct is_bf16 { static constexpr bool value = false; };
 template <> struct is_bf16<__hip_bfloat16> { static constexpr bool value = true; };

@@ -5,121 +5,86 @@
 // (fits the 4 KB kernarg budget), grid-stride over the total element count.
 // fp32 only (parameters, gradients and federation vectors are fp32 master).
 
-#include "fedkit_common.h"
+#include "multi_tensor.h"
 
 namespace {
 
-constexpr int kMaxTensors = 48;
-
-struct Desc {
-  const float* src[kMaxTensors];
-  float* dst[kMaxTensors];
-  long long offset[kMaxTensors + 1];  // prefix offsets into the flat vector
-  int n;
-};
-
-__device__ __forceinline__ int find_tensor(const Desc& d, long long i) {
-  // offsets are sorted; ~48 entries -> short scalar loop, mostly uniform
-  int lo = 0, hi = d.n - 1;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) >> 1;
-    if (i >= d.offset[mid]) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
+using fedkit_mt::DeviceGuard;
+using fedkit_mt::find_segment;
+using fedkit_mt::for_each_unit;
+using fedkit_mt::SegTable;
 
 // flat[off_t + j] = tensor_t[j]
-__global__ void pack_kernel(Desc d, float* __restrict__ flat, long long total) {
+__global__ void pack_kernel(SegTable<1> d, float* __restrict__ flat,
+                            long long total) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
        i < total; i += (long long)gridDim.x * blockDim.x) {
-    int t = find_tensor(d, i);
-    flat[i] = d.src[t][i - d.offset[t]];
+    int t = find_segment(d, i);
+    flat[i] = d.at<const float>(0, t)[i - d.offset[t]];
   }
 }
 
 // tensor_t[j] = flat[off_t + j]
-__global__ void unpack_kernel(Desc d, const float* __restrict__ flat,
+__global__ void unpack_kernel(SegTable<1> d, const float* __restrict__ flat,
                               long long total) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
        i < total; i += (long long)gridDim.x * blockDim.x) {
-    int t = find_tensor(d, i);
-    d.dst[t][i - d.offset[t]] = flat[i];
+    int t = find_segment(d, i);
+    d.at<float>(0, t)[i - d.offset[t]] = flat[i];
   }
 }
 
 // tensor_t[j] += alpha * flat[off_t + j]   (LBFGS _add_grad / axpy)
-__global__ void axpy_kernel(Desc d, const float* __restrict__ flat, float alpha,
-                            long long total) {
+__global__ void axpy_kernel(SegTable<1> d, const float* __restrict__ flat,
+                            float alpha, long long total) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
        i < total; i += (long long)gridDim.x * blockDim.x) {
-    int t = find_tensor(d, i);
-    d.dst[t][i - d.offset[t]] += alpha * flat[i];
+    int t = find_segment(d, i);
+    d.at<float>(0, t)[i - d.offset[t]] += alpha * flat[i];
   }
 }
 
 enum class Op { Pack, Unpack, Axpy };
 
-void run_chunks(const std::vector<at::Tensor>& tensors, const at::Tensor& flat,
-                Op op, float alpha) {
-  TORCH_CHECK(flat.is_contiguous() && flat.scalar_type() == at::kFloat,
-              "flat vector must be contiguous fp32");
-  long long flat_off = 0;
+void run_flat_op(const char* name, const std::vector<at::Tensor>& tensors,
+                 const at::Tensor& flat, Op op, float alpha) {
+  auto cs = fedkit_mt::build_chunks<1>(name, {&tensors}, {at::kFloat});
+  fedkit_mt::check_flat(name, "flat", flat, tensors[0], cs.total);
+  const DeviceGuard guard(tensors[0].device());
   auto stream = fedkit_stream();
-  size_t idx = 0;
-  while (idx < tensors.size()) {
-    Desc d;
-    d.n = 0;
-    long long base = flat_off;
-    while (idx < tensors.size() && d.n < kMaxTensors) {
-      const at::Tensor& t = tensors[idx];
-      TORCH_CHECK(t.scalar_type() == at::kFloat, "flat ops are fp32-only");
-      TORCH_CHECK(t.is_non_overlapping_and_dense(),
-                  "flat ops need dense tensors");
-      d.offset[d.n] = flat_off - base;
-      d.src[d.n] = (const float*)t.data_ptr();
-      d.dst[d.n] = (float*)t.data_ptr();
-      flat_off += t.numel();
-      ++d.n;
-      ++idx;
-    }
-    d.offset[d.n] = flat_off - base;
-    long long total = flat_off - base;
-    if (total == 0) continue;
-    const float* fsrc = (const float*)flat.data_ptr() + base;
-    float* fdst = (float*)flat.data_ptr() + base;
-    int grid = grid_1d(total, 256);
+  for (const auto& c : cs.chunks) {
+    float* f = flat.data_ptr<float>() + c.base;
+    int grid = grid_1d(c.total, 256);
     switch (op) {
       case Op::Pack:
         hipLaunchKernelGGL(pack_kernel, dim3(grid), dim3(256), 0, stream,
-                           d, fdst, total);
+                           c.d, f, c.total);
         break;
       case Op::Unpack:
         hipLaunchKernelGGL(unpack_kernel, dim3(grid), dim3(256), 0, stream,
-                           d, fsrc, total);
+                           c.d, (const float*)f, c.total);
         break;
       case Op::Axpy:
         hipLaunchKernelGGL(axpy_kernel, dim3(grid), dim3(256), 0, stream,
-                           d, fsrc, alpha, total);
+                           c.d, (const float*)f, alpha, c.total);
         break;
     }
   }
-  TORCH_CHECK(flat_off == flat.numel(),
-              "flat vector size mismatch: ", flat.numel(), " vs ", flat_off);
 }
 
 }  // namespace
 
 void fedkit_pack_params(std::vector<at::Tensor> tensors, at::Tensor flat) {
-  run_chunks(tensors, flat, Op::Pack, 0.f);
+  run_flat_op("pack_params", tensors, flat, Op::Pack, 0.f);
 }
 
 void fedkit_unpack_params(at::Tensor flat, std::vector<at::Tensor> tensors) {
-  run_chunks(tensors, flat, Op::Unpack, 0.f);
+  run_flat_op("unpack_params", tensors, flat, Op::Unpack, 0.f);
 }
 
 void fedkit_add_flat_params(std::vector<at::Tensor> tensors, at::Tensor flat,
                             double alpha) {
-  run_chunks(tensors, flat, Op::Axpy, (float)alpha);
+  run_flat_op("add_flat_params", tensors, flat, Op::Axpy, (float)alpha);
 }
 
 // ------------------------------------------------- L-BFGS fused multi-ops
@@ -171,18 +136,20 @@ __global__ void multi_dot_kernel(VecPack vp, const float* __restrict__ x,
   }
 }
 
-// out[v] = sum_b part[b][v] — one wave per column (nb <= 640 rows)
-__global__ void multi_dot_finalize_kernel(const float* __restrict__ part,
-                                          int nb, int nvec,
-                                          float* __restrict__ out) {
-  int v = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+// out[c] = sum_r part[r][c] — one wave per column, rows in a fixed order
+// (deterministic: no atomics).  The one finalize of every partials slab:
+// multi_dot here, the penalty / ADMM / BB reductions in consensus.hip.
+__global__ void colsum_finalize_kernel(const float* __restrict__ part,
+                                       int rows, int cols,
+                                       float* __restrict__ out) {
+  int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   int lane = threadIdx.x & 63;
-  if (v >= nvec) return;
+  if (c >= cols) return;
   float s = 0.f;
-  for (int b = lane; b < nb; b += 64) s += part[(long long)b * nvec + v];
+  for (int r = lane; r < rows; r += 64) s += part[(long long)r * cols + c];
 #pragma unroll
-  for (int off = 32; off; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) out[v] = s;
+  for (int off = 32; off; off >>= 1) s += __shfl_down(s, off, kWave);
+  if (lane == 0) out[c] = s;
 }
 
 // out[i] = cg * g[i] + sum_v c[v] * p[v][i]
@@ -199,6 +166,12 @@ __global__ void lincomb_kernel(CoefPack cp, const float* __restrict__ g,
 }
 
 }  // namespace
+
+void fedkit_colsum_finalize(const float* part, int rows, int cols, float* out,
+                            hipStream_t stream) {
+  hipLaunchKernelGGL(colsum_finalize_kernel, dim3((cols + 3) / 4), dim3(256),
+                     0, stream, part, rows, cols, out);
+}
 
 // returns a DEVICE fp32 tensor [len(vecs)] of dots x . vecs[i]; the caller
 // syncs once with .cpu() when it needs the scalars
@@ -223,9 +196,8 @@ at::Tensor fedkit_multi_dot(std::vector<at::Tensor> vecs,
   auto out = at::empty({vp.n}, x.options());
   hipLaunchKernelGGL(multi_dot_kernel, dim3(nb), dim3(256), 0, stream, vp,
                      x.data_ptr<float>(), total, part.data_ptr<float>());
-  hipLaunchKernelGGL(multi_dot_finalize_kernel,
-                     dim3((vp.n + 3) / 4), dim3(256), 0, stream,
-                     part.data_ptr<float>(), nb, vp.n, out.data_ptr<float>());
+  fedkit_colsum_finalize(part.data_ptr<float>(), nb, vp.n,
+                         out.data_ptr<float>(), stream);
   return out;
 }
 
@@ -257,134 +229,58 @@ at::Tensor fedkit_lincomb(const at::Tensor& g, double cg,
 // --------------------------------------------------- batched weight casts
 // In a full-model training step every FedConv2d pays one fp32->bf16 cast
 // kernel forward and one bf16->fp32 grad cast backward (~40 launches,
-// ~200 us/step on ResNet18).  One descriptor-table kernel covers all of
-// them per direction; layouts are preserved because dsts are allocated
-// *_like their srcs and both sides are traversed flat.
+// ~200 us/step on ResNet18).  One segment-table kernel covers all of them
+// per direction (one launch per 48 pairs); both sides are traversed flat,
+// and build_chunks() checks that each dst has its src's physical layout.
 
 namespace {
 
-struct CastDesc {
-  const void* src[kMaxTensors];
-  void* dst[kMaxTensors];
-  long long offset[kMaxTensors + 1];
-  int n;
-};
-
-__device__ __forceinline__ int cast_find(const CastDesc& d, long long i) {
-  int lo = 0, hi = d.n - 1;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) >> 1;
-    if (i >= d.offset[mid]) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// 8 elements per loop iteration (guide G13: 16-B/lane traffic): ONE
-// boundary search per unit, vector loads/stores on the in-tensor fast
-// path, scalar fallback only for units straddling a tensor boundary
-// (<= n units total).  The scalar original measured 68 us for the
-// ResNet18 grad-cast sweep — pure search+scalar-store overhead.
-__global__ void cast_f32_to_bf16_kernel(CastDesc d, long long total) {
-  typedef __attribute__((ext_vector_type(4))) float f4;
-  const long long units = (total + 7) >> 3;
-  for (long long u = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       u < units; u += (long long)gridDim.x * blockDim.x) {
-    long long i0 = u << 3;
-    int t = cast_find(d, i0);
-    long long j = i0 - d.offset[t];
-    if (i0 + 8 <= d.offset[t + 1]) {
-      const float* s = (const float*)d.src[t] + j;
-      __hip_bfloat16* p = (__hip_bfloat16*)d.dst[t] + j;
-      f4 a, b;
-      __builtin_memcpy(&a, s, 16);
-      __builtin_memcpy(&b, s + 4, 16);
-      __hip_bfloat16 o[8];
+// 8 elements per unit (guide G13: 16-B/lane traffic): vector loads/stores
+// on the in-tensor fast path, per-element fallback only for units
+// straddling a tensor boundary.  The scalar original measured 68 us for
+// the ResNet18 grad-cast sweep — pure search+scalar-store overhead.
+template <typename S, typename D>
+__global__ void cast_kernel(SegTable<2> d, long long total) {
+  for_each_unit<8>(
+      d, total,
+      [&](int t, long long j, long long) {
+        S in[8];
+        D out[8];
+        __builtin_memcpy(in, d.at<const S>(0, t) + j, sizeof(in));
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        o[k] = __float2bfloat16(a[k]);
-        o[4 + k] = __float2bfloat16(b[k]);
-      }
-      __builtin_memcpy(p, o, 16);
-    } else {
-      for (long long i = i0; i < i0 + 8 && i < total; ++i) {
-        int tt = cast_find(d, i);
-        long long jj = i - d.offset[tt];
-        ((__hip_bfloat16*)d.dst[tt])[jj] =
-            __float2bfloat16(((const float*)d.src[tt])[jj]);
-      }
-    }
-  }
+        for (int k = 0; k < 8; ++k) from_f32(to_f32(in[k]), out[k]);
+        __builtin_memcpy(d.at<D>(1, t) + j, out, sizeof(out));
+      },
+      [&](int t, long long j, long long) {
+        from_f32(to_f32(d.at<const S>(0, t)[j]), d.at<D>(1, t)[j]);
+      });
 }
 
-__global__ void cast_bf16_to_f32_kernel(CastDesc d, long long total) {
-  typedef __attribute__((ext_vector_type(4))) float f4;
-  const long long units = (total + 7) >> 3;
-  for (long long u = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       u < units; u += (long long)gridDim.x * blockDim.x) {
-    long long i0 = u << 3;
-    int t = cast_find(d, i0);
-    long long j = i0 - d.offset[t];
-    if (i0 + 8 <= d.offset[t + 1]) {
-      const __hip_bfloat16* s = (const __hip_bfloat16*)d.src[t] + j;
-      float* p = (float*)d.dst[t] + j;
-      __hip_bfloat16 in[8];
-      __builtin_memcpy(in, s, 16);
-      f4 a, b;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        a[k] = __bfloat162float(in[k]);
-        b[k] = __bfloat162float(in[4 + k]);
-      }
-      __builtin_memcpy(p, &a, 16);
-      __builtin_memcpy(p + 4, &b, 16);
-    } else {
-      for (long long i = i0; i < i0 + 8 && i < total; ++i) {
-        int tt = cast_find(d, i);
-        long long jj = i - d.offset[tt];
-        ((float*)d.dst[tt])[jj] =
-            __bfloat162float(((const __hip_bfloat16*)d.src[tt])[jj]);
-      }
-    }
-  }
-}
-
-CastDesc build_cast_desc(const std::vector<at::Tensor>& srcs,
-                         const std::vector<at::Tensor>& dsts,
-                         long long* total_out) {
-  TORCH_CHECK(srcs.size() == dsts.size() &&
-              (int)srcs.size() <= kMaxTensors,
-              "cast: 1..", kMaxTensors, " tensor pairs");
-  CastDesc d;
-  d.n = (int)srcs.size();
-  long long off = 0;
-  for (int i = 0; i < d.n; ++i) {
-    TORCH_CHECK(srcs[i].numel() == dsts[i].numel(), "cast: numel mismatch");
-    d.src[i] = srcs[i].data_ptr();
-    d.dst[i] = dsts[i].data_ptr();
-    d.offset[i] = off;
-    off += srcs[i].numel();
-  }
-  d.offset[d.n] = off;
-  *total_out = off;
-  return d;
+template <typename S, typename D>
+void run_cast(const char* name, const std::vector<at::Tensor>& srcs,
+              at::ScalarType src_dtype, const std::vector<at::Tensor>& dsts,
+              at::ScalarType dst_dtype) {
+  auto cs = fedkit_mt::build_chunks<2>(name, {&srcs, &dsts},
+                                       {src_dtype, dst_dtype});
+  const DeviceGuard guard(srcs[0].device());
+  auto stream = fedkit_stream();
+  for (const auto& c : cs.chunks)
+    hipLaunchKernelGGL((cast_kernel<S, D>), dim3(grid_1d(c.total, 256)),
+                       dim3(256), 0, stream, c.d, c.total);
 }
 
 }  // namespace
 
 void fedkit_cast_f32_to_bf16(std::vector<at::Tensor> srcs,
                              std::vector<at::Tensor> dsts) {
-  long long total;
-  auto d = build_cast_desc(srcs, dsts, &total);
-  hipLaunchKernelGGL(cast_f32_to_bf16_kernel, dim3(grid_1d(total, 256)),
-                     dim3(256), 0, fedkit_stream(), d, total);
+  run_cast<float, __hip_bfloat16>("cast_f32_to_bf16", srcs, at::kFloat, dsts,
+                                  at::kBFloat16);
 }
 
 void fedkit_cast_bf16_to_f32(std::vector<at::Tensor> srcs,
                              std::vector<at::Tensor> dsts) {
-  long long total;
-  auto d = build_cast_desc(srcs, dsts, &total);
-  hipLaunchKernelGGL(cast_bf16_to_f32_kernel, dim3(grid_1d(total, 256)),
-                     dim3(256), 0, fedkit_stream(), d, total);
+  run_cast<__hip_bfloat16, float>("cast_bf16_to_f32", srcs, at::kBFloat16,
+                                  dsts, at::kFloat);
 }
 
 // ------------------------------------------------- fused Welford update

@@ -156,7 +156,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lincomb", &fedkit_lincomb,
         "cg*g + sum c[i]*vecs[i] in one pass (L-BFGS direction build)");
   m.def("cast_f32_to_bf16", &fedkit_cast_f32_to_bf16,
-        "batched fp32->bf16 tensor casts (one kernel for <=48 tensors)");
+        "batched fp32->bf16 tensor casts (one launch per 48 tensors)");
   m.def("cast_bf16_to_f32", &fedkit_cast_bf16_to_f32,
         "batched bf16->fp32 tensor casts");
   m.def("penalty_fwd", &fedkit_penalty_fwd,

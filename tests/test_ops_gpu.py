@@ -92,6 +92,96 @@ def test_pack_many_tensors_chunking():
     assert torch.equal(flat, torch.cat(ts))
 
 
+def _cast_sources():
+    """Numels around the 8-wide cast unit — units start in one tensor and
+    end in another, the last unit is a tail — plus a channels_last 4-D."""
+    torch.manual_seed(5)
+    ts = [torch.randn(n, device="cuda") for n in (0, 1, 7, 8, 9, 15, 16, 17)]
+    ts.append(torch.randn(8, 3, 3, 3, device="cuda").contiguous(
+        memory_format=torch.channels_last))
+    return ts
+
+
+def _check_cast_roundtrip(ext, srcs):
+    lo = [torch.zeros_like(s, dtype=torch.bfloat16) for s in srcs]
+    ext.cast_f32_to_bf16(srcs, lo)
+    for s, d in zip(srcs, lo):
+        assert d.stride() == s.stride()
+        assert torch.equal(d, s.to(torch.bfloat16))
+    hi = [torch.zeros_like(d, dtype=torch.float32) for d in lo]
+    ext.cast_bf16_to_f32(lo, hi)
+    for d, h in zip(lo, hi):
+        assert h.stride() == d.stride()
+        assert torch.equal(h, d.float())
+
+
+def test_batched_casts_direct():
+    _check_cast_roundtrip(_ext(), _cast_sources())
+
+
+def test_batched_casts_past_one_table():
+    """50 tensors: two 48-tensor tables, one launch each."""
+    torch.manual_seed(6)
+    _check_cast_roundtrip(
+        _ext(), [torch.randn(7, device="cuda") for _ in range(50)])
+
+
+def _assert_rejected_untouched(fn, outputs):
+    """fn must raise before any launch: outputs stay bit-unchanged."""
+    before = [t.clone() for t in outputs]
+    with pytest.raises(RuntimeError):
+        fn()
+    torch.cuda.synchronize()
+    for t, b in zip(outputs, before):
+        assert t.dtype == b.dtype and torch.equal(t, b)
+
+
+@pytest.mark.parametrize("flat_kind", ["short", "cpu"])
+@pytest.mark.parametrize("op", ["pack", "unpack", "axpy"])
+def test_flat_ops_reject_bad_flat_before_launch(op, flat_kind):
+    ext = _ext()
+    torch.manual_seed(7)
+    ts = [torch.randn(n, device="cuda") for n in (5, 8, 3)]
+    flat = torch.randn(15 if flat_kind == "short" else 16,
+                       device="cuda" if flat_kind == "short" else "cpu")
+    call = {"pack": lambda: ext.pack_params(ts, flat),
+            "unpack": lambda: ext.unpack_params(flat, ts),
+            "axpy": lambda: ext.add_flat_params(ts, flat, 0.5)}[op]
+    _assert_rejected_untouched(call, ts + [flat])
+
+
+def test_add_flat_rejects_late_bad_dtype_before_launch():
+    """The bad tensor sits in the second table; the first 48 stay put."""
+    ext = _ext()
+    torch.manual_seed(8)
+    ts = [torch.randn(7, device="cuda") for _ in range(49)]
+    ts.append(torch.randn(7, device="cuda").half())
+    flat = torch.randn(7 * 50, device="cuda")
+    _assert_rejected_untouched(
+        lambda: ext.add_flat_params(ts, flat, 0.5), ts)
+
+
+@pytest.mark.parametrize("case", ["src_dtype", "numel", "layout"])
+def test_cast_rejects_mismatch_before_launch(case):
+    ext = _ext()
+    torch.manual_seed(9)
+    src = torch.randn(8, 3, 3, 3, device="cuda")
+    if case == "src_dtype":
+        src = src.to(torch.bfloat16)
+        dst = torch.zeros_like(src)
+    elif case == "numel":
+        dst = torch.zeros(8, 3, 3, 2, device="cuda", dtype=torch.bfloat16)
+    else:
+        src = src.contiguous(memory_format=torch.channels_last)
+        dst = torch.zeros(8, 3, 3, 3, device="cuda", dtype=torch.bfloat16)
+        assert dst.stride() != src.stride()
+    good = torch.randn(9, device="cuda")
+    good_dst = torch.zeros(9, device="cuda", dtype=torch.bfloat16)
+    _assert_rejected_untouched(
+        lambda: ext.cast_f32_to_bf16([good, src], [good_dst, dst]),
+        [good_dst, dst])
+
+
 # ----------------------------------------------------------------------- loss
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -1187,6 +1277,49 @@ def test_fused_adam_matches_torch_adam():
         # second moment: g*g accumulation order differs (fma vs addcmul),
         # measured 1.3e-5 relative after 10 steps — rounding, not math
         assert frob_err(m1["exp_avg_sq"], m2["exp_avg_sq"]) < 1e-4
+
+
+def test_fused_adam_past_one_table():
+    """50 parameters (two 48-tensor tables) of numels around the 4-wide
+    unit, two steps, against torch.optim.Adam."""
+    from fedkit.optim import FusedAdam
+    torch.manual_seed(48)
+    numels = [(1, 3, 4, 5, 7)[i % 5] for i in range(50)]
+    p1 = [torch.randn(n, device="cuda", requires_grad=True) for n in numels]
+    p2 = [p.detach().clone().requires_grad_(True) for p in p1]
+    o1 = FusedAdam(p1, lr=3e-3, weight_decay=0.01)
+    o2 = torch.optim.Adam(p2, lr=3e-3, weight_decay=0.01)
+    for it in range(2):
+        torch.manual_seed(200 + it)
+        for a, b in zip(p1, p2):
+            a.grad = torch.randn_like(a)
+            b.grad = a.grad.clone()
+        o1.step()
+        o2.step()
+    for a, b in zip(p1, p2):
+        assert frob_err(a, b) < 1e-5
+    for m1, m2 in zip(o1.state_dict()["state"].values(),
+                      o2.state_dict()["state"].values()):
+        assert frob_err(m1["exp_avg"], m2["exp_avg"]) < 1e-5
+        assert frob_err(m1["exp_avg_sq"], m2["exp_avg_sq"]) < 1e-4
+
+
+@pytest.mark.parametrize("case", ["late_state_dtype", "grad_numel"])
+def test_adam_step_rejects_before_launch(case):
+    ext = _ext()
+    torch.manual_seed(49)
+    n = 50 if case == "late_state_dtype" else 3
+    ps = [torch.randn(7, device="cuda") for _ in range(n)]
+    gs = [torch.randn(7, device="cuda") for _ in range(n)]
+    ms = [torch.randn(7, device="cuda") for _ in range(n)]
+    vs = [torch.rand(7, device="cuda") for _ in range(n)]
+    if case == "late_state_dtype":
+        vs[-1] = vs[-1].to(torch.bfloat16)
+    else:
+        gs[1] = torch.randn(6, device="cuda")
+    _assert_rejected_untouched(
+        lambda: ext.adam_step(ps, gs, ms, vs, 1e-3, 0.9, 0.999, 1e-8, 1, 0.0),
+        ps + ms + vs)
 
 
 def test_fused_adam_bumps_param_versions():
