@@ -60,15 +60,19 @@ __device__ __forceinline__ void store4(float* p, f4 v) {
   }
 }
 
-// Sum of v over the 256-thread workgroup, valid in thread 0.  Wave64
-// shuffle tree, then the four wave sums in index order: a fixed order.
+// Sum of v over the 256-thread workgroup (NW = 4 waves; 128 threads with
+// NW = 2), valid in thread 0.  Wave64 shuffle tree, then the wave sums in
+// index order: a fixed order.
+template <int NW = 4>
 __device__ __forceinline__ float block_sum(float v, float* red /* [4] */) {
+  static_assert(NW == 4 || NW == 2, "256- or 128-thread workgroups");
 #pragma unroll
   for (int off = 32; off; off >>= 1) v += __shfl_down(v, off, kWave);
   __syncthreads();   // red may still be read from a previous call
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
+  if constexpr (NW == 2) return red[0] + red[1];
+  else return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 template <bool HZ, bool HY>
@@ -151,8 +155,25 @@ penalty_bwd_kernel(SegTable<1> d, const float* __restrict__ z,
       });
 }
 
+// rho (x - z), rounded: it is added to y as torch's `y.add_(rho * (x - z))`
+// adds it, not fused into the add, so that this kernel, aggregate_kernel
+// and the torch sequence leave the same bits in y.
+__device__ __forceinline__ float dual_step(float rho, float x, float z) {
+#pragma clang fp contract(off)
+  return rho * (x - z);
+}
+
+__device__ __forceinline__ float add_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// kernels whose results are compared bit for bit: no packed fp32 ALU forms
+#define FEDKIT_AGG_KERNEL \
+  __global__ void __attribute__((target("no-packed-fp32-ops")))
+
 // y += rho (x - z);  part[blockIdx.x] = partial sum of (rho (x - z))^2
-__global__ void __launch_bounds__(kBlock)
+FEDKIT_AGG_KERNEL __launch_bounds__(kBlock)
 admm_dual_update_kernel(float* __restrict__ y, const float* __restrict__ x,
                         const float* __restrict__ z, float rho, long long n,
                         float* __restrict__ part) {
@@ -166,15 +187,15 @@ admm_dual_update_kernel(float* __restrict__ y, const float* __restrict__ x,
       f4 xv = load4(x + i0), zv = load4(z + i0), yv = load4(y + i0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        float yd = rho * (xv[k] - zv[k]);
-        yv[k] += yd;
+        float yd = dual_step(rho, xv[k], zv[k]);
+        yv[k] = add_rounded(yv[k], yd);
         acc += yd * yd;
       }
       store4(y + i0, yv);
     } else {
       for (long long i = i0; i < n; ++i) {
-        float yd = rho * (x[i] - z[i]);
-        y[i] += yd;
+        float yd = dual_step(rho, x[i], z[i]);
+        y[i] = add_rounded(y[i], yd);
         acc += yd * yd;
       }
     }
@@ -222,6 +243,211 @@ bb_stats_kernel(const float* __restrict__ y, const float* __restrict__ yh,
     float s = block_sum(acc[c], red);
     if (threadIdx.x == 0) part[(long long)blockIdx.x * 6 + c] = s;
   }
+}
+
+// ---- aggregation round: z-update, dual update and residuals in one pass ----
+//
+// One LocalComm round over K client vectors x_k (and duals y_k for ADMM):
+//   fedavg   znew = (0 + x_0 + ... + x_{K-1}) * inv          inv = 1/K
+//   fedprox  same znew;  r_k = sum (rho (x_k - znew))^2
+//   admm     znew = (0 + c_0 + ...) * inv, c_k = y_k + rho x_k, inv = 1/(K rho)
+//            y_k += rho (x_k - znew);  r_k as above
+// and r_z = sum (z - znew)^2 in every mode.  Every operand is read once and
+// znew / y_k are written once: a thread's unit (4 consecutive floats) keeps
+// its K client values on chip between the sum and the residual / dual step.
+//
+// Bit-compatibility with the torch sequence the strategies ran before (K
+// in-place adds into a zero vector, `/= scalar`, `rho * (x - znew)`, `add_`):
+// contraction is off in this code, every product is rounded before it is
+// added, the sum starts from +0.0f and runs in client order, and the
+// division is a multiply by a reciprocal formed on the host.  Found on
+// gfx950: torch's GPU division of a float tensor by a host scalar s is
+// `t * inv` bit for bit, not the correctly rounded quotient (which differs
+// in 20% of the elements at s = 10 and 33% at s = 3), and inv is
+// (float)(1.0 / s) with s and the division in double: 1.0f / (float)s is a
+// different float at, e.g., s = 17 * 0.1 and misses torch's znew by 1-2 ulp.
+//
+// Variants: the held values live in registers up to K = 16 in both modes,
+// template-unrolled in buckets of 4 clients (K is a run-time argument; a
+// bucket costs at most 12 (fedprox) or 24 (admm) VGPRs it does not use).
+// Above 16 clients a thread parks them in a private LDS column
+// ([rows][BLOCK] float4, 128 KB: one workgroup per CU); a thread reads back
+// only what it wrote, so the slab needs no barrier, and consecutive lanes
+// touch consecutive 16-byte slots, so it has no bank conflicts.  The
+// cut-over is at 16 because registers are the better store up to there: the
+// largest register variant, 16 clients with duals, still runs 2 waves per
+// SIMD (8 per CU, each with 33 16-byte loads in flight per lane) against the
+// slab's 4 (fedprox, 256 threads) or 2 (admm, 128 threads) waves per CU,
+// and the drivers' default K = 10 runs 5 (fedprox) or 3 (admm) waves per
+// SIMD.  Past 16 the admm registers (2 x 4 x K) would drop it to one wave.
+// The per-variant figures are in the table at fedkit_aggregate_round.
+// FedAvg forms no per-client residual and holds nothing.  The n % 4 tail
+// elements are done after the unit loop, one thread each, so the loop body
+// has no tail branch.
+
+constexpr int kMaxClients = 32;
+constexpr int kAggRegMax = 16;   // clients held in registers; above: LDS
+enum { kFedAvg = 0, kFedProx = 1, kAdmm = 2 };
+
+struct ClientTable {              // by value in the kernarg segment, 512 B
+  const float* x[kMaxClients];
+  float* y[kMaxClients];
+};
+
+// A unit of 4 floats at i0; lanes at or past n read as 0 and are not stored.
+// Zero lanes add exact zeros to every sum below.
+__device__ __forceinline__ f4 load_unit(const float* p, long long i0,
+                                        long long n) {
+  if (i0 + 4 <= n) return load4(p + i0);
+  f4 v = {};
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (i0 + e < n) v[e] = p[i0 + e];
+  return v;
+}
+
+__device__ __forceinline__ void store_unit(float* p, long long i0, long long n,
+                                           f4 v) {
+  if (i0 + 4 <= n) {
+    store4(p + i0, v);
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (i0 + e < n) p[i0 + e] = v[e];
+}
+
+// znew = (0 + x_0 + ...) * inv;  part[blockIdx.x] = partial sum (z - znew)^2
+FEDKIT_AGG_KERNEL __launch_bounds__(kBlock)
+aggregate_fedavg_kernel(ClientTable t, const float* __restrict__ z,
+                        float* __restrict__ znew, float inv, int K,
+                        long long n, float* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ float red[4];
+  float acc = 0.f;
+  const long long units = (n + 3) >> 2;
+  for (long long u = blockIdx.x * (long long)kBlock + threadIdx.x; u < units;
+       u += (long long)gridDim.x * kBlock) {
+    const long long i0 = u << 2;
+    f4 s = {};
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) s += load_unit(t.x[k], i0, n);
+    f4 zn = s * inv;
+    f4 d = load_unit(z, i0, n) - zn;
+    store_unit(znew, i0, n, zn);
+    acc += d[0] * d[0];
+    acc += d[1] * d[1];
+    acc += d[2] * d[2];
+    acc += d[3] * d[3];
+  }
+  float r = block_sum(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+
+// FedProx / ADMM round for K <= KL clients.  LDS = false: held values in
+// registers (hx, hy).  LDS = true: in the thread's column of `slab`.
+// part[blockIdx.x][0] = partial sum (z - znew)^2, [1 + k] = partial r_k.
+template <int MODE, int KL, bool LDS, int BLOCK>
+FEDKIT_AGG_KERNEL __launch_bounds__(BLOCK)
+aggregate_kernel(ClientTable t, const float* __restrict__ z,
+                 float* __restrict__ znew, float rho, float inv, int K,
+                 long long n, float* __restrict__ part) {
+#pragma clang fp contract(off)
+  constexpr bool DUAL = MODE == kAdmm;
+  constexpr int ROWS = DUAL ? 2 * KL : KL;
+  __shared__ f4 slab[LDS ? ROWS * BLOCK : 1];
+  __shared__ float red[4];
+  f4 hx[LDS ? 1 : KL], hy[(LDS || !DUAL) ? 1 : KL];
+  const int tid = threadIdx.x;
+  // slot of client k in this thread's slab column: x rows, then y rows
+  const int col = tid;
+#define AGG_PUT(regs, row, k, v)                       \
+  do {                                                 \
+    if constexpr (LDS) slab[((row) + (k)) * BLOCK + col] = (v); \
+    else regs[k] = (v);                                \
+  } while (0)
+#define AGG_GET(regs, row, k) \
+  (LDS ? slab[((row) + (k)) * BLOCK + col] : regs[LDS ? 0 : (k)])
+  float accz = 0.f, acck[KL] = {};
+  const long long units = n >> 2;   // whole units; the tail follows the loop
+  for (long long u = blockIdx.x * (long long)BLOCK + tid; u < units;
+       u += (long long)gridDim.x * BLOCK) {
+    const long long i0 = u << 2;
+    // all loads of the unit are issued before the first use
+#pragma unroll
+    for (int k = 0; k < KL; ++k)
+      if (k < K) {
+        AGG_PUT(hx, 0, k, load4(t.x[k] + i0));
+        if constexpr (DUAL) AGG_PUT(hy, KL, k, load4(t.y[k] + i0));
+      }
+    const f4 zv = load4(z + i0);
+    f4 s = {};
+#pragma unroll
+    for (int k = 0; k < KL; ++k)
+      if (k < K) {
+        f4 c = AGG_GET(hx, 0, k);
+        if constexpr (DUAL) c = AGG_GET(hy, KL, k) + rho * c;
+        s += c;
+      }
+    const f4 zn = s * inv;
+    store4(znew + i0, zn);
+    const f4 d = zv - zn;
+    accz += d[0] * d[0];
+    accz += d[1] * d[1];
+    accz += d[2] * d[2];
+    accz += d[3] * d[3];
+#pragma unroll
+    for (int k = 0; k < KL; ++k)
+      if (k < K) {
+        const f4 yd = rho * (AGG_GET(hx, 0, k) - zn);
+        if constexpr (DUAL) store4(t.y[k] + i0, AGG_GET(hy, KL, k) + yd);
+        acck[k] += yd[0] * yd[0];
+        acck[k] += yd[1] * yd[1];
+        acck[k] += yd[2] * yd[2];
+        acck[k] += yd[3] * yd[3];
+      }
+  }
+  // the n % 4 tail elements: one thread each, same arithmetic per element
+  const long long it = (units << 2) + tid;
+  if (blockIdx.x == 0 && it < n) {
+    float xs[KL], s = 0.f;
+#pragma unroll
+    for (int k = 0; k < KL; ++k)
+      if (k < K) {
+        xs[k] = t.x[k][it];
+        s += DUAL ? t.y[k][it] + rho * xs[k] : xs[k];
+      }
+    const float zn = s * inv, d = z[it] - zn;
+    znew[it] = zn;
+    accz += d * d;
+#pragma unroll
+    for (int k = 0; k < KL; ++k)
+      if (k < K) {
+        const float yd = rho * (xs[k] - zn);
+        if constexpr (DUAL) t.y[k][it] += yd;
+        acck[k] += yd * yd;
+      }
+  }
+  float* row = part + (long long)blockIdx.x * (1 + K);
+  float r = block_sum<BLOCK / kWave>(accz, red);
+  if (tid == 0) row[0] = r;
+#pragma unroll
+  for (int k = 0; k < KL; ++k)
+    if (k < K) {
+      r = block_sum<BLOCK / kWave>(acck[k], red);
+      if (tid == 0) row[1 + k] = r;
+    }
+#undef AGG_PUT
+#undef AGG_GET
+}
+
+template <int MODE, int KL, bool LDS, int BLOCK>
+void launch_aggregate(const ClientTable& t, const float* z, float* znew,
+                      float rho, float inv, int K, long long n, int nb,
+                      float* part, hipStream_t stream) {
+  hipLaunchKernelGGL((aggregate_kernel<MODE, KL, LDS, BLOCK>), dim3(nb),
+                     dim3(BLOCK), 0, stream, t, z, znew, rho, inv, K, n,
+                     part);
 }
 
 const float* flat_ptr(const c10::optional<at::Tensor>& v, long long n,
@@ -373,4 +599,104 @@ at::Tensor fedkit_bb_stats(const at::Tensor& y, const at::Tensor& yhat0,
   fedkit_colsum_finalize(part.data_ptr<float>(), nb, 6,
                          out.data_ptr<float>(), stream);
   return out;
+}
+
+// One LocalComm aggregation round (see aggregate_kernel).  Returns
+// {znew, res}: znew a fresh fp32 [N]; res device fp32, res[0] =
+// sum (z - znew)^2 and, in fedprox / admm mode, res[1 + k] =
+// sum (rho (x_k - znew))^2.  admm updates ys[k] += rho (xs[k] - znew) in
+// place.  mode: 0 fedavg, 1 fedprox, 2 admm.
+//
+// Compiler's kernel-resource-usage figures for gfx950 (no variant uses
+// scratch; 512 VGPRs per SIMD lane):
+//   variant             threads  VGPRs  LDS bytes  waves/SIMD
+//   fedavg, any K         256      38        16        8
+//   fedprox K <=  4 reg   256      40        16        8
+//   fedprox K <=  8 reg   256      60        16        8
+//   fedprox K <= 12 reg   256      81        16        5
+//   fedprox K <= 16 reg   256     104        16        4
+//   fedprox K <= 32 LDS   256     122    131088        1 (one workgroup/CU)
+//   admm    K <=  4 reg   256      63        16        8
+//   admm    K <=  8 reg   256     100        16        4
+//   admm    K <= 12 reg   256     136        16        3
+//   admm    K <= 16 reg   256     188        16        2
+//   admm    K <= 32 LDS   128     138    131088        2 waves per CU
+std::vector<at::Tensor> fedkit_aggregate_round(std::vector<at::Tensor> xs,
+                                               const at::Tensor& z,
+                                               std::vector<at::Tensor> ys,
+                                               double rho, int64_t mode) {
+  const char* op = "aggregate_round";
+  TORCH_CHECK(mode == kFedAvg || mode == kFedProx || mode == kAdmm, op,
+              ": unknown mode ", mode);
+  const int K = (int)xs.size();
+  TORCH_CHECK(xs.size() >= 1 && xs.size() <= (size_t)kMaxClients, op,
+              ": 1..", kMaxClients, " clients, got ", xs.size());
+  if (mode == kAdmm) {
+    TORCH_CHECK(ys.size() == xs.size(), op, ": ", ys.size(), " duals for ",
+                xs.size(), " clients");
+    TORCH_CHECK(rho > 0.0 && std::isfinite(rho), op,
+                ": admm needs a finite rho > 0, got ", rho);
+  } else {
+    TORCH_CHECK(ys.empty(), op, ": duals are an admm operand");
+    TORCH_CHECK(mode == kFedAvg || std::isfinite(rho), op,
+                ": fedprox needs a finite rho, got ", rho);
+  }
+  const long long n = z.numel();
+  fedkit_mt::check_flat(op, "z", z, z, n);
+  ClientTable t = {};
+  for (int k = 0; k < K; ++k) {
+    fedkit_mt::check_flat(op, "every x_k", xs[k], z, n);
+    t.x[k] = xs[k].data_ptr<float>();
+  }
+  for (size_t k = 0; k < ys.size(); ++k) {
+    fedkit_mt::check_flat(op, "every y_k", ys[k], z, n);
+    t.y[k] = ys[k].data_ptr<float>();
+    // y_k is written while the other operands are still being read
+    TORCH_CHECK(n == 0 || t.y[k] != z.data_ptr<float>(), op,
+                ": y_k aliases z");
+    for (int j = 0; j < K; ++j)
+      TORCH_CHECK(n == 0 || (t.y[k] != t.x[j] && (j >= (int)k ||
+                                                  t.y[k] != t.y[j])),
+                  op, ": y_", k, " aliases another operand");
+  }
+  const DeviceGuard guard(z.device());
+  const int cols = mode == kFedAvg ? 1 : 1 + K;
+  auto znew = at::empty({n}, z.options());
+  if (n == 0) return {znew, at::zeros({cols}, z.options())};
+  auto res = at::empty({cols}, z.options());
+  auto stream = fedkit_stream();
+  const bool lds = mode != kFedAvg && K > kAggRegMax;
+  const int block = (lds && mode == kAdmm) ? 128 : kBlock;
+  const int nb = grid_1d((n + 3) >> 2, block, kRedGrid);
+  auto part = at::empty({nb, cols}, z.options());
+  const float* zp = z.data_ptr<float>();
+  float* np = znew.data_ptr<float>();
+  float* pp = part.data_ptr<float>();
+  const float r = (float)rho;
+  // the reciprocal torch forms for `znew /= K` and `znew /= (K * rho)`:
+  // in double from the double scalar, then rounded to fp32
+  const float inv =
+      (float)(1.0 / (mode == kAdmm ? (double)K * rho : (double)K));
+#define FEDKIT_AGG_LAUNCH(MODE, KL, LDS, BLOCK) \
+  launch_aggregate<MODE, KL, LDS, BLOCK>(t, zp, np, r, inv, K, n, nb, pp, \
+                                         stream)
+  if (mode == kFedAvg) {
+    hipLaunchKernelGGL(aggregate_fedavg_kernel, dim3(nb), dim3(kBlock), 0,
+                       stream, t, zp, np, inv, K, n, pp);
+  } else if (mode == kFedProx) {
+    if (K <= 4) FEDKIT_AGG_LAUNCH(kFedProx, 4, false, kBlock);
+    else if (K <= 8) FEDKIT_AGG_LAUNCH(kFedProx, 8, false, kBlock);
+    else if (K <= 12) FEDKIT_AGG_LAUNCH(kFedProx, 12, false, kBlock);
+    else if (K <= 16) FEDKIT_AGG_LAUNCH(kFedProx, 16, false, kBlock);
+    else FEDKIT_AGG_LAUNCH(kFedProx, 32, true, kBlock);
+  } else {
+    if (K <= 4) FEDKIT_AGG_LAUNCH(kAdmm, 4, false, kBlock);
+    else if (K <= 8) FEDKIT_AGG_LAUNCH(kAdmm, 8, false, kBlock);
+    else if (K <= 12) FEDKIT_AGG_LAUNCH(kAdmm, 12, false, kBlock);
+    else if (K <= 16) FEDKIT_AGG_LAUNCH(kAdmm, 16, false, kBlock);
+    else FEDKIT_AGG_LAUNCH(kAdmm, 32, true, 128);
+  }
+#undef FEDKIT_AGG_LAUNCH
+  fedkit_colsum_finalize(pp, nb, cols, res.data_ptr<float>(), stream);
+  return {znew, res};
 }

@@ -55,6 +55,11 @@ class Strategy:
     name = "base"
     writeback_z = False     # does aggregate() write z back into the models?
     uses_penalty = False    # does the closure add a penalty term?
+    # GPU, every client in this process (LocalComm), K <= 32: run the round
+    # as ONE pass of consensus.aggregate_round instead of the torch
+    # sequence.  z and y come out bitwise the same; False restores the
+    # sequence (FedConfig.fused_aggregate).
+    fused_aggregate = True
 
     def init_block(self, comm: Communicator, N: int, device,
                    x0: Optional[Dict[int, torch.Tensor]] = None,
@@ -75,6 +80,12 @@ class Strategy:
                   x: Dict[int, torch.Tensor], round_idx: int) -> dict:
         """Run the communication round; returns log info.  Updates state."""
         raise NotImplementedError
+
+    def _fused_round(self, comm: Communicator, state: dict,
+                     x: Dict[int, torch.Tensor]) -> bool:
+        return (self.fused_aggregate and len(x) == comm.K
+                and comm.K <= consensus.MAX_FUSED_CLIENTS
+                and native_enabled(state["z"]))
 
     # -- split form: start() launches the collective (comm stream), finish()
     #    consumes it.  The engine can slot independent work (test-set eval
@@ -103,11 +114,19 @@ class FedAvg(Strategy):
     writeback_z = True
 
     def aggregate_start(self, comm, state, x):
+        if self._fused_round(comm, state, x):
+            return None     # no clones, no collective: finish() does it all
         return comm.sum_across_clients_async(
             {k: v.clone() for k, v in x.items()})
 
     def aggregate_finish(self, comm, state, x, pending, round_idx):
         z, N = state["z"], state["N"]
+        if pending is None:
+            # one pass: znew and sum (z - znew)^2, still no host sync
+            znew, res = consensus.aggregate_round(
+                [x[ck] for ck in sorted(x)], z, mode="fedavg")
+            state["z"] = znew
+            return {"dual": torch.sqrt(res[0]) / N}
         znew = pending()
         znew /= comm.K
         # device-side residual, NO host sync here: the engine enqueues the
@@ -170,6 +189,8 @@ class FedProx(Strategy):
                 "rho": self._rho(state.get("block_idx", 0), ck)}
 
     def aggregate_start(self, comm, state, x):
+        if self._fused_round(comm, state, x):
+            return None     # no clones, no collective: finish() does it all
         return comm.sum_across_clients_async(
             {k: v.clone() for k, v in x.items()})
 
@@ -180,13 +201,22 @@ class FedProx(Strategy):
 
     def aggregate_finish(self, comm, state, x, pending, round_idx):
         z, N, rho = state["z"], state["N"], state["rho"]
-        znew = pending()
-        znew /= comm.K
-        dual_residual = torch.norm(z - znew).item() / N
+        if pending is None:
+            # one pass, then ONE host read of the 1 + K squared norms
+            cks = sorted(x)
+            znew, res = consensus.aggregate_round(
+                [x[ck] for ck in cks], z, rho=rho, mode="fedprox")
+            sq = res.tolist()
+            dual_residual = math.sqrt(sq[0]) / N
+            per_client = {ck: [math.sqrt(v)] for ck, v in zip(cks, sq[1:])}
+        else:
+            znew = pending()
+            znew /= comm.K
+            dual_residual = torch.norm(z - znew).item() / N
+            # primal residual: sum_k ||rho (x_k - znew)|| / N  (fedprox_multi.py:228-232)
+            per_client = {ck: [torch.norm(rho * (xv - znew)).item()]
+                          for ck, xv in x.items()}
         state["z"] = znew
-        # primal residual: sum_k ||rho (x_k - znew)|| / N  (fedprox_multi.py:228-232)
-        per_client = {ck: [torch.norm(rho * (xv - znew)).item()]
-                      for ck, xv in x.items()}
         rows = comm.gather_scalar_rows(per_client)
         primal_residual = float(rows[:, 0].sum()) / N
         state["round"] = round_idx + 1
@@ -300,6 +330,20 @@ class ConsensusADMM(Strategy):
             self._bb_update(comm, state, x, round_idx)
         rho = state["rho"]
         z = state["z"]
+        if self._fused_round(comm, state, x):
+            # z-update, every dual update and the 1 + K squared residual
+            # norms in one pass, then ONE host read
+            cks = sorted(x)
+            znew, res = consensus.aggregate_round(
+                [x[ck] for ck in cks], z, [state["y"][ck] for ck in cks],
+                rho=rho, mode="admm")
+            state["z"] = znew
+            sq = res.tolist()
+            rows = comm.gather_scalar_rows(
+                {ck: [math.sqrt(v)] for ck, v in zip(cks, sq[1:])})
+            state["round"] = round_idx + 1
+            return {"dual": math.sqrt(sq[0]) / N,
+                    "primal": float(rows[:, 0].sum()) / N, "rho": rho}
         # z-update: (1/(K rho)) sum_k (y_k + rho x_k)  (consensus_multi.py:281-285)
         contrib = {ck: state["y"][ck] + rho * x[ck] for ck in x}
         znew = comm.sum_across_clients(contrib)

@@ -12,6 +12,8 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
   add_elu_fwd / add_elu_bwd      fused residual-add + ELU
   penalty_fwd / penalty_bwd      fused FedProx/ADMM penalty + L1/L2 regulariser
   admm_dual_update / bb_stats    fused ADMM y-update and BB inner products
+  aggregate_round                one-pass K-client round: z-update, dual
+                                 update and residuals (FedAvg/FedProx/ADMM)
 
 Dispatch policy (this is the "native code is THE path that runs" rule):
   * on a ROCm GPU the HIP kernels are used; if the extension is missing the

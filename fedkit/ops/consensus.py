@@ -11,7 +11,9 @@ parameter tensors in place and differentiates it with ONE elementwise
 kernel writing the closed-form gradient (csrc/consensus.hip) — no cat of
 the block, no autograd tape over a dozen elementwise ops.  The aggregation
 side has `admm_dual_update` (y += rho (x-z) fused with the primal-residual
-norm) and `bb_stats` (the six Barzilai-Borwein inner products in one pass).
+norm) and `bb_stats` (the six Barzilai-Borwein inner products in one pass);
+`aggregate_round` runs a whole round of K local clients (z-update, dual
+update, residuals) as one pass over the operands.
 
 All vectors are fp32 in PHYSICAL (storage) element order, the order
 flat.pack / paramvec.flat_physical use.  Dispatch follows the package rule:
@@ -112,6 +114,56 @@ def admm_dual_update(y: torch.Tensor, x: torch.Tensor, z: torch.Tensor,
     ydelta = rho * (x - z)
     y.add_(ydelta)
     return torch.norm(ydelta) ** 2
+
+
+AGGREGATE_MODES = ("fedavg", "fedprox", "admm")
+MAX_FUSED_CLIENTS = 32     # kMaxClients of csrc/consensus.hip
+
+
+def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                    ys: Optional[Sequence[torch.Tensor]] = None,
+                    rho: Optional[float] = None, mode: str = "fedavg"):
+    """One aggregation round over the K client vectors `xs` held in this
+    process; returns (znew, res).
+
+      fedavg   znew = (x_0 + ... + x_{K-1}) / K
+      fedprox  same znew
+      admm     znew = sum_k (y_k + rho x_k) / (K rho), then
+               ys[k] += rho (xs[k] - znew) in place
+
+    `res` is fp32 on z's device: res[0] = sum (z - znew)^2 and, except in
+    fedavg mode, res[1 + k] = sum (rho (xs[k] - znew))^2.  `z` and `xs` are
+    not modified and znew is a new tensor.  On the GPU this is one pass over
+    the operands (csrc/consensus.hip, 1 <= K <= 32) whose znew and ys are
+    bitwise those of the torch sequence below.
+    """
+    assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+    xs = list(xs)
+    ys = list(ys) if ys is not None else []
+    if mode == "admm":
+        assert len(ys) == len(xs), "admm needs one dual vector per client"
+    if mode != "fedavg":
+        assert rho is not None, f"{mode} needs rho"
+    if _use_native(z):
+        from . import require_ext
+        znew, res = require_ext().aggregate_round(
+            xs, z, ys if mode == "admm" else [],
+            0.0 if rho is None else float(rho), AGGREGATE_MODES.index(mode))
+        return znew, res
+    K = len(xs)
+    contrib = [y + rho * x for x, y in zip(xs, ys)] if mode == "admm" else xs
+    znew = torch.zeros_like(contrib[0])
+    for c in contrib:
+        znew += c
+    znew /= (K * rho) if mode == "admm" else K
+    res = [torch.norm(z - znew) ** 2]
+    if mode != "fedavg":
+        for k, x in enumerate(xs):
+            ydelta = rho * (x - znew)
+            res.append(torch.norm(ydelta) ** 2)
+            if mode == "admm":
+                ys[k].add_(ydelta)
+    return znew, torch.stack(res)
 
 
 def bb_stats(y: torch.Tensor, yhat0: torch.Tensor, x: torch.Tensor,

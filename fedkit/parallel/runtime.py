@@ -106,6 +106,10 @@ class FedConfig:
     fused_penalty: bool = True         # GPU: FedProx/ADMM penalty + L1/L2
                                        # regulariser as one fused HIP op
                                        # (False = the torch expression)
+    fused_aggregate: bool = True       # GPU, all K clients in one process,
+                                       # K <= 32: the aggregation round as
+                                       # one fused HIP pass (False = the
+                                       # torch sequence; same z and y bits)
 
     def model_name(self) -> str:
         if self.model:
@@ -113,6 +117,11 @@ class FedConfig:
         return "ResNet18" if self.use_resnet else "Net"
 
     def make_strategy(self) -> Strategy:
+        strategy = self._make_strategy()
+        strategy.fused_aggregate = self.fused_aggregate
+        return strategy
+
+    def _make_strategy(self) -> Strategy:
         if self.strategy == "none":
             return NoConsensus()
         if self.strategy == "fedavg":

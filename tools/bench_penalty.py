@@ -2,7 +2,7 @@
 """Microbenchmark: fused consensus penalty / ADMM statistics vs the torch
 expressions they replace, same process, same inputs.
 
-    python tools/bench_penalty.py [--out FILE.md]
+    python tools/bench_penalty.py [--out FILE.md] [--section NAME]
 
 Two parameter lists: Net2's largest fc block (fc4: [1024,512] + [1024]) and
 ResNet18's last conv block (two channels_last [512,512,3,3] weights + four
@@ -13,6 +13,14 @@ Timed per list, for each of the two paths:
   fwd       value only under no_grad (an LBFGS line-search probe)
 and bb_stats against the six-dot form (device time, and wall time including
 the host read of the six numbers, which is how the BB update consumes them).
+
+Section `aggregate`: one aggregation round of K = 10 local clients,
+consensus.aggregate_round against the torch sequence the strategies run
+with --fused_aggregate 0 (clones, K adds, divide, norms, per-client dual
+update), for fedavg / fedprox / admm at the ResNet18 last conv block's N and
+at its linear head's N (512*10 + 10).  Device time, and for fedprox / admm
+wall time including the host reads of the residuals (one .tolist() against
+K+1 .item() calls).
 
 Method: warm-up, then SAMPLES samples per path taken alternately (fused,
 torch, fused, ...), each sample ITERS back-to-back calls between two device
@@ -103,9 +111,70 @@ def ab(fn_a, fn_b, sampler=sample_us):
             max(a) - min(a), max(b) - min(b))
 
 
+AGG_K = 10
+AGG_SIZES = {"ResNet18 last conv block": 4720640, "ResNet18 head": 5130}
+
+
+def torch_round(xs, z, ys, mode, read):
+    """The strategies' sequence without the fused round (GPU form)."""
+    K = len(xs)
+    if mode == "admm":
+        contrib = [y + RHO * x for x, y in zip(xs, ys)]
+    else:
+        contrib = [x.clone() for x in xs]
+    znew = torch.zeros_like(contrib[0])
+    for c in contrib:
+        znew += c
+    znew /= (K * RHO) if mode == "admm" else K
+    dual = torch.norm(z - znew)
+    if mode == "fedavg":
+        return dual
+    out = [dual.item() if read else dual]
+    for k, x in enumerate(xs):
+        if mode == "admm":
+            sq = consensus.admm_dual_update(ys[k], x, znew, RHO)
+        else:
+            sq = torch.norm(RHO * (x - znew))
+        out.append(sq.item() if read else sq)
+    return out
+
+
+def aggregate_section(dev, row):
+    for name, n in AGG_SIZES.items():
+        g = torch.Generator().manual_seed(2)
+        xs = [(torch.randn(n, generator=g) * 0.05).to(dev)
+              for _ in range(AGG_K)]
+        z = (torch.randn(n, generator=g) * 0.05).to(dev)
+        for mode in consensus.AGGREGATE_MODES:
+            # duals start at 0 and are updated by every timed call of either
+            # path; with constant x they stay finite (y_k sums to ~0)
+            ya = [torch.zeros(n, device=dev) for _ in range(AGG_K)]
+            yb = [torch.zeros(n, device=dev) for _ in range(AGG_K)]
+            ys = lambda y: y if mode == "admm" else None  # noqa: E731
+
+            def fused(read=False):
+                znew, res = consensus.aggregate_round(xs, z, ys(ya), rho=RHO,
+                                                      mode=mode)
+                return res.tolist() if read else res
+
+            zf, _ = consensus.aggregate_round(xs, z, ys([y.clone() for y in ya]),
+                                              rho=RHO, mode=mode)
+            print(f"{name} {mode}: znew finite {bool(zf.isfinite().all())}",
+                  flush=True)
+            row(f"{name}: {mode} round K={AGG_K} (device)", n,
+                ab(fused, lambda: torch_round(xs, z, yb, mode, False)))
+            if mode != "fedavg":
+                row(f"{name}: {mode} round K={AGG_K} (wall, with host reads)",
+                    n, ab(lambda: fused(True),
+                          lambda: torch_round(xs, z, yb, mode, True),
+                          sampler=sample_wall_us))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table here")
+    ap.add_argument("--section", default="all",
+                    choices=["all", "penalty", "aggregate"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_penalty needs a GPU")
@@ -120,7 +189,8 @@ def main():
                      f"| {sa:.1f} / {sb:.1f} |")
         print(lines[-1], flush=True)
 
-    for name, params in param_lists(dev).items():
+    plists = param_lists(dev) if args.section != "aggregate" else {}
+    for name, params in plists.items():
         n = sum(p.numel() for p in params)
         g = torch.Generator().manual_seed(1)
         z = torch.randn(n, generator=g).to(dev) * 0.05
@@ -183,6 +253,9 @@ def main():
 
         row(f"{name}: admm_dual_update (device)", n,
             ab(lambda: consensus.admm_dual_update(yy, x, z, RHO), dual_torch))
+
+    if args.section != "penalty":
+        aggregate_section(dev, row)
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
