@@ -15,7 +15,8 @@
 //
 // The aggregation side gets the same treatment: admm_dual_update fuses
 // y += rho (x-z) with the primal-residual norm, bb_stats forms the six
-// Barzilai-Borwein inner products in one pass over five vectors.
+// Barzilai-Borwein inner products in one pass over five vectors
+// (bb_stats_round: for all local clients in one launch).
 //
 // Every reduction is deterministic: fixed grid (a function of the length
 // only), per-workgroup partials in a slab, one finalize kernel that sums
@@ -29,6 +30,9 @@
 // straddle a tensor boundary or the tail take a per-element scalar path.
 
 #include "multi_tensor.h"
+
+#include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -204,19 +208,24 @@ admm_dual_update_kernel(float* __restrict__ y, const float* __restrict__ x,
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
+// One element's six products, each folded into its sum by one fused
+// multiply-add.  The fma is written out: left to contraction, the compiler
+// fused some of these and rounded the product of others, differently from
+// one kernel to the next, and bb_stats_round_kernel's rows have to be
+// bb_stats_kernel's bit for bit.
 __device__ __forceinline__ void bb_accum(float* acc, float y, float yh,
                                          float x, float z, float x0) {
   float a = y - yh, b = x - z, dx = x - x0;
-  acc[0] += a * a;
-  acc[1] += a * b;
-  acc[2] += b * b;
-  acc[3] += a * dx;
-  acc[4] += b * dx;
-  acc[5] += dx * dx;
+  acc[0] = __builtin_fmaf(a, a, acc[0]);
+  acc[1] = __builtin_fmaf(a, b, acc[1]);
+  acc[2] = __builtin_fmaf(b, b, acc[2]);
+  acc[3] = __builtin_fmaf(a, dx, acc[3]);
+  acc[4] = __builtin_fmaf(b, dx, acc[4]);
+  acc[5] = __builtin_fmaf(dx, dx, acc[5]);
 }
 
 // part[blockIdx.x][0..5] = partial (a.a, a.b, b.b, a.dx, b.dx, dx.dx)
-__global__ void __launch_bounds__(kBlock)
+FEDKIT_AGG_KERNEL __launch_bounds__(kBlock)
 bb_stats_kernel(const float* __restrict__ y, const float* __restrict__ yh,
                 const float* __restrict__ x, const float* __restrict__ z,
                 const float* __restrict__ x0, long long n,
@@ -243,6 +252,92 @@ bb_stats_kernel(const float* __restrict__ y, const float* __restrict__ yh,
     float s = block_sum(acc[c], red);
     if (threadIdx.x == 0) part[(long long)blockIdx.x * 6 + c] = s;
   }
+}
+
+constexpr int kMaxClients = 32;
+
+// ---- BB statistics of all K local clients in one launch ----
+//
+// bb_stats_kernel once per client reads z K times and costs K launches and K
+// host reads.  Here blockIdx.y picks a bucket of kBBBucket clients out of a
+// table in the kernarg segment; a thread loads its z unit once and serves
+// the bucket's clients from it: four 16-byte loads and six accumulators per
+// client.  z is read ceil(K / kBBBucket) times.
+//
+// Row k is bitwise bb_stats of client k, which keeps the BB rho chain (and
+// so z and y) the same whichever path formed the statistics: per client this
+// is bb_stats_kernel's partition (same grid over the units, same unit of a
+// thread, same in-loop tail), the same bb_accum with its explicit fmas, the
+// same block_sum, and a finalize whose row order depends on the number of
+// workgroups only.
+//
+// Bucket size, from the compiler's kernel-resource-usage report for gfx950
+// (256 threads, 16 B LDS, no scratch in any of them):
+//   clients/bucket  VGPRs  waves/SIMD  z reads at K = 10
+//         2           43       7              5
+//         4           57       7              3
+//         8           83       5              2
+// 4 is used: it costs no occupancy against 2 and reads z 3 times at the
+// drivers' default K = 10 where bb_stats read it 10 times.  8 saves one more
+// read of z there, but gives up two waves per SIMD and leaves 6 of its 16
+// client slots idle.  (bb_stats_kernel: 35 VGPRs, 8 waves.)
+constexpr int kBBBucket = 4;
+
+struct BBTable {                  // by value in the kernarg segment, 1 KB
+  const float* y[kMaxClients];
+  const float* yh[kMaxClients];
+  const float* x[kMaxClients];
+  const float* x0[kMaxClients];
+};
+
+// part[blockIdx.x][k][0..5] = workgroup partial of client k's six products
+FEDKIT_AGG_KERNEL __launch_bounds__(kBlock)
+bb_stats_round_kernel(BBTable t, const float* __restrict__ z, int K,
+                      long long n, float* __restrict__ part) {
+  __shared__ float red[4];
+  const int k0 = blockIdx.y * kBBBucket;   // wave-uniform: scalar table reads
+  const float *py[kBBBucket], *ph[kBBBucket], *px[kBBBucket], *pp[kBBBucket];
+#pragma unroll
+  for (int j = 0; j < kBBBucket; ++j) {
+    const int k = min(k0 + j, K - 1);      // slots past K are never read
+    py[j] = t.y[k]; ph[j] = t.yh[k]; px[j] = t.x[k]; pp[j] = t.x0[k];
+  }
+  float acc[kBBBucket][6] = {};
+  const long long units = (n + 3) >> 2;
+  for (long long u = blockIdx.x * (long long)kBlock + threadIdx.x; u < units;
+       u += (long long)gridDim.x * kBlock) {
+    long long i0 = u << 2;
+    if (i0 + 4 <= n) {
+      const f4 zv = load4(z + i0);
+#pragma unroll
+      for (int j = 0; j < kBBBucket; ++j)
+        if (k0 + j < K) {
+          f4 yv = load4(py[j] + i0), hv = load4(ph[j] + i0),
+             xv = load4(px[j] + i0), pv = load4(pp[j] + i0);
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            bb_accum(acc[j], yv[e], hv[e], xv[e], zv[e], pv[e]);
+        }
+    } else {
+      for (long long i = i0; i < n; ++i) {
+        const float zs = z[i];
+#pragma unroll
+        for (int j = 0; j < kBBBucket; ++j)
+          if (k0 + j < K)
+            bb_accum(acc[j], py[j][i], ph[j][i], px[j][i], zs, pp[j][i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kBBBucket; ++j)
+    if (k0 + j < K) {
+      float* row = part + ((long long)blockIdx.x * K + k0 + j) * 6;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        float s = block_sum(acc[j][c], red);
+        if (threadIdx.x == 0) row[c] = s;
+      }
+    }
 }
 
 // ---- aggregation round: z-update, dual update and residuals in one pass ----
@@ -284,15 +379,37 @@ bb_stats_kernel(const float* __restrict__ y, const float* __restrict__ yh,
 // FedAvg forms no per-client residual and holds nothing.  The n % 4 tail
 // elements are done after the unit loop, one thread each, so the loop body
 // has no tail branch.
+//
+// BB carry (admm only): adaptive rho also wants, from the operands this
+// kernel already holds on chip,
+//   x0_k = x_k        yhat0_k = y_k + rho_used[k] (x_k - z)
+// with y_k before the dual step and the old z.  A compile-time CARRY adds
+// them as one (kCarryX0, round 0) or two (kCarryFull) more 16-byte stores per
+// client and no load.  rho_used is the rho the BB chain had at client k's
+// turn; it travels by value and is indexed by the unrolled client index
+// only, so it stays in scalar registers.  Without carry the kernel takes an
+// empty argument in the table's place and is the code it was.
 
-constexpr int kMaxClients = 32;
 constexpr int kAggRegMax = 16;   // clients held in registers; above: LDS
 enum { kFedAvg = 0, kFedProx = 1, kAdmm = 2 };
+// ints, not an unnamed enum: CARRY is part of aggregate_kernel's signature
+// (CarryArg<CARRY>), and an unnamed type in a kernel's mangled name is
+// numbered differently by the host and the device compilation
+constexpr int kCarryNone = 0, kCarryX0 = 1, kCarryFull = 2;
 
 struct ClientTable {              // by value in the kernarg segment, 512 B
   const float* x[kMaxClients];
   float* y[kMaxClients];
 };
+
+struct CarryTable {               // by value in the kernarg segment, 640 B
+  float* x0[kMaxClients];
+  float* yh[kMaxClients];
+  float rho_used[kMaxClients];
+};
+struct NoCarry {};
+template <int CARRY>
+using CarryArg = std::conditional_t<CARRY == kCarryNone, NoCarry, CarryTable>;
 
 // A unit of 4 floats at i0; lanes at or past n read as 0 and are not stored.
 // Zero lanes add exact zeros to every sum below.
@@ -347,13 +464,15 @@ aggregate_fedavg_kernel(ClientTable t, const float* __restrict__ z,
 // FedProx / ADMM round for K <= KL clients.  LDS = false: held values in
 // registers (hx, hy).  LDS = true: in the thread's column of `slab`.
 // part[blockIdx.x][0] = partial sum (z - znew)^2, [1 + k] = partial r_k.
-template <int MODE, int KL, bool LDS, int BLOCK>
+// CARRY: also write cr.x0[k] (kCarryX0) and cr.yh[k] (kCarryFull).
+template <int MODE, int KL, bool LDS, int BLOCK, int CARRY>
 FEDKIT_AGG_KERNEL __launch_bounds__(BLOCK)
 aggregate_kernel(ClientTable t, const float* __restrict__ z,
                  float* __restrict__ znew, float rho, float inv, int K,
-                 long long n, float* __restrict__ part) {
+                 long long n, float* __restrict__ part, CarryArg<CARRY> cr) {
 #pragma clang fp contract(off)
   constexpr bool DUAL = MODE == kAdmm;
+  static_assert(DUAL || CARRY == kCarryNone, "the BB carry is an admm step");
   constexpr int ROWS = DUAL ? 2 * KL : KL;
   __shared__ f4 slab[LDS ? ROWS * BLOCK : 1];
   __shared__ float red[4];
@@ -373,6 +492,13 @@ aggregate_kernel(ClientTable t, const float* __restrict__ z,
   for (long long u = blockIdx.x * (long long)BLOCK + tid; u < units;
        u += (long long)gridDim.x * BLOCK) {
     const long long i0 = u << 2;
+    // Slab variant with carry: 128 pointers and 32 rho values are more than
+    // the SGPR file; held live across this loop they made the compiler
+    // reserve a private segment.  An offset it cannot see through has it
+    // read the carry table's entries per unit instead (scalar loads that
+    // hit the scalar cache), and no variant has a private segment.
+    int ko = 0;
+    if constexpr (LDS && CARRY != kCarryNone) asm volatile("" : "+s"(ko));
     // all loads of the unit are issued before the first use
 #pragma unroll
     for (int k = 0; k < KL; ++k)
@@ -400,6 +526,12 @@ aggregate_kernel(ClientTable t, const float* __restrict__ z,
     for (int k = 0; k < KL; ++k)
       if (k < K) {
         const f4 yd = rho * (AGG_GET(hx, 0, k) - zn);
+        if constexpr (CARRY != kCarryNone)
+          store4(cr.x0[k + ko] + i0, AGG_GET(hx, 0, k));
+        if constexpr (CARRY == kCarryFull)
+          store4(cr.yh[k + ko] + i0,
+                 AGG_GET(hy, KL, k) +
+                     cr.rho_used[k + ko] * (AGG_GET(hx, 0, k) - zv));
         if constexpr (DUAL) store4(t.y[k] + i0, AGG_GET(hy, KL, k) + yd);
         acck[k] += yd[0] * yd[0];
         acck[k] += yd[1] * yd[1];
@@ -417,13 +549,16 @@ aggregate_kernel(ClientTable t, const float* __restrict__ z,
         xs[k] = t.x[k][it];
         s += DUAL ? t.y[k][it] + rho * xs[k] : xs[k];
       }
-    const float zn = s * inv, d = z[it] - zn;
+    const float zo = z[it], zn = s * inv, d = zo - zn;
     znew[it] = zn;
     accz += d * d;
 #pragma unroll
     for (int k = 0; k < KL; ++k)
       if (k < K) {
         const float yd = rho * (xs[k] - zn);
+        if constexpr (CARRY != kCarryNone) cr.x0[k][it] = xs[k];
+        if constexpr (CARRY == kCarryFull)
+          cr.yh[k][it] = t.y[k][it] + cr.rho_used[k] * (xs[k] - zo);
         if constexpr (DUAL) t.y[k][it] += yd;
         acck[k] += yd * yd;
       }
@@ -441,13 +576,42 @@ aggregate_kernel(ClientTable t, const float* __restrict__ z,
 #undef AGG_GET
 }
 
-template <int MODE, int KL, bool LDS, int BLOCK>
-void launch_aggregate(const ClientTable& t, const float* z, float* znew,
-                      float rho, float inv, int K, long long n, int nb,
-                      float* part, hipStream_t stream) {
-  hipLaunchKernelGGL((aggregate_kernel<MODE, KL, LDS, BLOCK>), dim3(nb),
-                     dim3(BLOCK), 0, stream, t, z, znew, rho, inv, K, n,
-                     part);
+struct AggArgs {                  // what every round variant is launched with
+  ClientTable t;
+  const float* z;
+  float* znew;
+  float rho, inv;
+  int K;
+  long long n;
+  int nb;
+  float* part;
+  hipStream_t stream;
+};
+
+template <int MODE, int KL, bool LDS, int BLOCK, int CARRY>
+void launch_aggregate(const AggArgs& a, const CarryArg<CARRY>& cr) {
+  hipLaunchKernelGGL((aggregate_kernel<MODE, KL, LDS, BLOCK, CARRY>),
+                     dim3(a.nb), dim3(BLOCK), 0, a.stream, a.t, a.z, a.znew,
+                     a.rho, a.inv, a.K, a.n, a.part, cr);
+}
+
+// the register variant that fits K, or the LDS slab above kAggRegMax
+template <int MODE, int CARRY>
+void launch_round(const AggArgs& a, const CarryArg<CARRY>& cr) {
+  constexpr int kSlabBlock = MODE == kAdmm ? 128 : kBlock;
+  if (a.K <= 4) launch_aggregate<MODE, 4, false, kBlock, CARRY>(a, cr);
+  else if (a.K <= 8) launch_aggregate<MODE, 8, false, kBlock, CARRY>(a, cr);
+  else if (a.K <= 12) launch_aggregate<MODE, 12, false, kBlock, CARRY>(a, cr);
+  else if (a.K <= kAggRegMax)
+    launch_aggregate<MODE, 16, false, kBlock, CARRY>(a, cr);
+  else launch_aggregate<MODE, 32, true, kSlabBlock, CARRY>(a, cr);
+}
+
+// [p, p + numel) of two operands intersect
+bool overlaps(const at::Tensor& a, const at::Tensor& b) {
+  const char* a0 = static_cast<const char*>(a.data_ptr());
+  const char* b0 = static_cast<const char*>(b.data_ptr());
+  return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
 }
 
 const float* flat_ptr(const c10::optional<at::Tensor>& v, long long n,
@@ -601,11 +765,60 @@ at::Tensor fedkit_bb_stats(const at::Tensor& y, const at::Tensor& yhat0,
   return out;
 }
 
+// device fp32 [K, 6]: row k = fedkit_bb_stats(ys[k], yhat0s[k], xs[k], z,
+// x0s[k]) bit for bit, for all K <= 32 clients in one launch + the finalize
+at::Tensor fedkit_bb_stats_round(std::vector<at::Tensor> ys,
+                                 std::vector<at::Tensor> yhat0s,
+                                 std::vector<at::Tensor> xs,
+                                 const at::Tensor& z,
+                                 std::vector<at::Tensor> x0s) {
+  const char* op = "bb_stats_round";
+  const int K = (int)xs.size();
+  TORCH_CHECK(xs.size() >= 1 && xs.size() <= (size_t)kMaxClients, op,
+              ": 1..", kMaxClients, " clients, got ", xs.size());
+  TORCH_CHECK(ys.size() == xs.size() && yhat0s.size() == xs.size() &&
+              x0s.size() == xs.size(), op, ": ", xs.size(), " clients but ",
+              ys.size(), " y, ", yhat0s.size(), " yhat0, ", x0s.size(),
+              " x0");
+  const long long n = z.numel();
+  fedkit_mt::check_flat(op, "z", z, z, n);
+  BBTable t = {};
+  for (int k = 0; k < K; ++k) {
+    fedkit_mt::check_flat(op, "every y_k", ys[k], z, n);
+    fedkit_mt::check_flat(op, "every yhat0_k", yhat0s[k], z, n);
+    fedkit_mt::check_flat(op, "every x_k", xs[k], z, n);
+    fedkit_mt::check_flat(op, "every x0_k", x0s[k], z, n);
+    t.y[k] = ys[k].data_ptr<float>();
+    t.yh[k] = yhat0s[k].data_ptr<float>();
+    t.x[k] = xs[k].data_ptr<float>();
+    t.x0[k] = x0s[k].data_ptr<float>();
+  }
+  const DeviceGuard guard(z.device());
+  if (n == 0) return at::zeros({K, 6}, z.options());
+  auto out = at::empty({K, 6}, z.options());
+  auto stream = fedkit_stream();
+  // bb_stats' grid: the partition of a client's sum must not depend on K
+  const int nb = grid_1d((n + 3) >> 2, kBlock, kRedGrid);
+  auto part = at::empty({nb, 6 * K}, z.options());
+  hipLaunchKernelGGL(bb_stats_round_kernel,
+                     dim3(nb, (K + kBBBucket - 1) / kBBBucket), dim3(kBlock),
+                     0, stream, t, z.data_ptr<float>(), K, n,
+                     part.data_ptr<float>());
+  fedkit_colsum_finalize(part.data_ptr<float>(), nb, 6 * K,
+                         out.data_ptr<float>(), stream);
+  return out;
+}
+
 // One LocalComm aggregation round (see aggregate_kernel).  Returns
 // {znew, res}: znew a fresh fp32 [N]; res device fp32, res[0] =
 // sum (z - znew)^2 and, in fedprox / admm mode, res[1 + k] =
 // sum (rho (x_k - znew))^2.  admm updates ys[k] += rho (xs[k] - znew) in
 // place.  mode: 0 fedavg, 1 fedprox, 2 admm.
+//
+// BB carry (admm): with x0s the round also writes x0s[k] = xs[k]; with
+// x0s, yhat0s and rho_used (K finite values) also yhat0s[k] = ys[k] +
+// rho_used[k] (xs[k] - z), from ys[k] as it came in and the old z.  The
+// outputs may not overlap any operand or each other.
 //
 // Compiler's kernel-resource-usage figures for gfx950 (no variant uses
 // scratch; 512 VGPRs per SIMD lane):
@@ -621,10 +834,18 @@ at::Tensor fedkit_bb_stats(const at::Tensor& y, const at::Tensor& yhat0,
 //   admm    K <= 12 reg   256     136        16        3
 //   admm    K <= 16 reg   256     188        16        2
 //   admm    K <= 32 LDS   128     138    131088        2 waves per CU
-std::vector<at::Tensor> fedkit_aggregate_round(std::vector<at::Tensor> xs,
-                                               const at::Tensor& z,
-                                               std::vector<at::Tensor> ys,
-                                               double rho, int64_t mode) {
+// and of the admm variants with the BB carry (VGPRs x0-only / full; LDS
+// bytes and waves as in the row above them, except K <= 4 full: 7 waves):
+//   admm    K <=  4 reg   256    63 /  64
+//   admm    K <=  8 reg   256   107 / 108
+//   admm    K <= 12 reg   256   137 / 138
+//   admm    K <= 16 reg   256   188 / 190
+//   admm    K <= 32 LDS   128   137 / 141
+std::vector<at::Tensor> fedkit_aggregate_round(
+    std::vector<at::Tensor> xs, const at::Tensor& z,
+    std::vector<at::Tensor> ys, double rho, int64_t mode,
+    std::vector<at::Tensor> x0s, std::vector<at::Tensor> yhat0s,
+    std::vector<double> rho_used) {
   const char* op = "aggregate_round";
   TORCH_CHECK(mode == kFedAvg || mode == kFedProx || mode == kAdmm, op,
               ": unknown mode ", mode);
@@ -640,6 +861,22 @@ std::vector<at::Tensor> fedkit_aggregate_round(std::vector<at::Tensor> xs,
     TORCH_CHECK(ys.empty(), op, ": duals are an admm operand");
     TORCH_CHECK(mode == kFedAvg || std::isfinite(rho), op,
                 ": fedprox needs a finite rho, got ", rho);
+    TORCH_CHECK(x0s.empty() && yhat0s.empty() && rho_used.empty(), op,
+                ": the BB carry (x0s, yhat0s, rho_used) is an admm operand");
+  }
+  const int carry = !yhat0s.empty() || !rho_used.empty() ? kCarryFull
+                    : !x0s.empty()                       ? kCarryX0
+                                                         : kCarryNone;
+  if (carry != kCarryNone)
+    TORCH_CHECK(x0s.size() == xs.size(), op, ": ", x0s.size(), " x0 for ",
+                xs.size(), " clients");
+  if (carry == kCarryFull) {
+    TORCH_CHECK(yhat0s.size() == xs.size() && rho_used.size() == xs.size(),
+                op, ": the full carry needs ", xs.size(),
+                " yhat0 and rho_used, got ", yhat0s.size(), " and ",
+                rho_used.size());
+    for (double r : rho_used)
+      TORCH_CHECK(std::isfinite(r), op, ": rho_used must be finite, got ", r);
   }
   const long long n = z.numel();
   fedkit_mt::check_flat(op, "z", z, z, n);
@@ -659,6 +896,25 @@ std::vector<at::Tensor> fedkit_aggregate_round(std::vector<at::Tensor> xs,
                                                   t.y[k] != t.y[j])),
                   op, ": y_", k, " aliases another operand");
   }
+  CarryTable cr = {};
+  std::vector<const at::Tensor*> outs;   // carry outputs checked so far
+  for (size_t i = 0; i < x0s.size() + yhat0s.size(); ++i) {
+    const bool is_x0 = i < x0s.size();
+    const size_t k = is_x0 ? i : i - x0s.size();
+    const at::Tensor& o = is_x0 ? x0s[k] : yhat0s[k];
+    fedkit_mt::check_flat(op, is_x0 ? "every x0_k" : "every yhat0_k", o, z, n);
+    (is_x0 ? cr.x0 : cr.yh)[k] = o.data_ptr<float>();
+    // written while every operand is still being read
+    bool clash = n > 0 && overlaps(o, z);
+    for (int j = 0; j < K && n > 0; ++j)
+      clash = clash || overlaps(o, xs[j]) || overlaps(o, ys[j]);
+    for (const at::Tensor* p : outs) clash = clash || (n > 0 && overlaps(o, *p));
+    TORCH_CHECK(!clash, op, ": ", is_x0 ? "x0_" : "yhat0_", k,
+                " overlaps another operand");
+    outs.push_back(&o);
+  }
+  for (size_t k = 0; k < rho_used.size(); ++k)
+    cr.rho_used[k] = (float)rho_used[k];
   const DeviceGuard guard(z.device());
   const int cols = mode == kFedAvg ? 1 : 1 + K;
   auto znew = at::empty({n}, z.options());
@@ -669,34 +925,25 @@ std::vector<at::Tensor> fedkit_aggregate_round(std::vector<at::Tensor> xs,
   const int block = (lds && mode == kAdmm) ? 128 : kBlock;
   const int nb = grid_1d((n + 3) >> 2, block, kRedGrid);
   auto part = at::empty({nb, cols}, z.options());
-  const float* zp = z.data_ptr<float>();
-  float* np = znew.data_ptr<float>();
   float* pp = part.data_ptr<float>();
-  const float r = (float)rho;
   // the reciprocal torch forms for `znew /= K` and `znew /= (K * rho)`:
   // in double from the double scalar, then rounded to fp32
   const float inv =
       (float)(1.0 / (mode == kAdmm ? (double)K * rho : (double)K));
-#define FEDKIT_AGG_LAUNCH(MODE, KL, LDS, BLOCK) \
-  launch_aggregate<MODE, KL, LDS, BLOCK>(t, zp, np, r, inv, K, n, nb, pp, \
-                                         stream)
+  const AggArgs a = {t, z.data_ptr<float>(), znew.data_ptr<float>(),
+                     (float)rho, inv, K, n, nb, pp, stream};
   if (mode == kFedAvg) {
     hipLaunchKernelGGL(aggregate_fedavg_kernel, dim3(nb), dim3(kBlock), 0,
-                       stream, t, zp, np, inv, K, n, pp);
+                       stream, t, a.z, a.znew, inv, K, n, pp);
   } else if (mode == kFedProx) {
-    if (K <= 4) FEDKIT_AGG_LAUNCH(kFedProx, 4, false, kBlock);
-    else if (K <= 8) FEDKIT_AGG_LAUNCH(kFedProx, 8, false, kBlock);
-    else if (K <= 12) FEDKIT_AGG_LAUNCH(kFedProx, 12, false, kBlock);
-    else if (K <= 16) FEDKIT_AGG_LAUNCH(kFedProx, 16, false, kBlock);
-    else FEDKIT_AGG_LAUNCH(kFedProx, 32, true, kBlock);
+    launch_round<kFedProx, kCarryNone>(a, NoCarry{});
+  } else if (carry == kCarryNone) {
+    launch_round<kAdmm, kCarryNone>(a, NoCarry{});
+  } else if (carry == kCarryX0) {
+    launch_round<kAdmm, kCarryX0>(a, cr);
   } else {
-    if (K <= 4) FEDKIT_AGG_LAUNCH(kAdmm, 4, false, kBlock);
-    else if (K <= 8) FEDKIT_AGG_LAUNCH(kAdmm, 8, false, kBlock);
-    else if (K <= 12) FEDKIT_AGG_LAUNCH(kAdmm, 12, false, kBlock);
-    else if (K <= 16) FEDKIT_AGG_LAUNCH(kAdmm, 16, false, kBlock);
-    else FEDKIT_AGG_LAUNCH(kAdmm, 32, true, 128);
+    launch_round<kAdmm, kCarryFull>(a, cr);
   }
-#undef FEDKIT_AGG_LAUNCH
   fedkit_colsum_finalize(pp, nb, cols, res.data_ptr<float>(), stream);
   return {znew, res};
 }

@@ -43,10 +43,16 @@ at::Tensor fedkit_admm_dual_update(at::Tensor y, const at::Tensor& x,
 at::Tensor fedkit_bb_stats(const at::Tensor& y, const at::Tensor& yhat0,
                            const at::Tensor& x, const at::Tensor& z,
                            const at::Tensor& x0);
-std::vector<at::Tensor> fedkit_aggregate_round(std::vector<at::Tensor> xs,
-                                               const at::Tensor& z,
-                                               std::vector<at::Tensor> ys,
-                                               double rho, int64_t mode);
+at::Tensor fedkit_bb_stats_round(std::vector<at::Tensor> ys,
+                                 std::vector<at::Tensor> yhat0s,
+                                 std::vector<at::Tensor> xs,
+                                 const at::Tensor& z,
+                                 std::vector<at::Tensor> x0s);
+std::vector<at::Tensor> fedkit_aggregate_round(
+    std::vector<at::Tensor> xs, const at::Tensor& z,
+    std::vector<at::Tensor> ys, double rho, int64_t mode,
+    std::vector<at::Tensor> x0s, std::vector<at::Tensor> yhat0s,
+    std::vector<double> rho_used);
 
 std::vector<at::Tensor> fedkit_cross_entropy_fwd(const at::Tensor& logits,
                                                  const at::Tensor& labels);
@@ -176,12 +182,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "y += rho (x - z) in place; returns device sum (rho (x - z))^2");
   m.def("bb_stats", &fedkit_bb_stats,
         "six Barzilai-Borwein inner products in one pass -> device fp32 [6]");
+  m.def("bb_stats_round", &fedkit_bb_stats_round,
+        "bb_stats of K <= 32 clients against one z in one pass -> device "
+        "fp32 [K, 6], row k bitwise bb_stats of client k",
+        py::arg("ys"), py::arg("yhat0s"), py::arg("xs"), py::arg("z"),
+        py::arg("x0s"));
   m.def("aggregate_round", &fedkit_aggregate_round,
         "one-pass K-client aggregation round (mode 0 fedavg, 1 fedprox, "
         "2 admm): returns (znew, res) with res[0] = sum (z - znew)^2 and "
-        "res[1 + k] = sum (rho (x_k - znew))^2; admm updates ys in place",
+        "res[1 + k] = sum (rho (x_k - znew))^2; admm updates ys in place "
+        "and, as the BB carry, writes x0s[k] = xs[k] and yhat0s[k] = ys[k] + "
+        "rho_used[k] (xs[k] - z) from the incoming ys and z",
         py::arg("xs"), py::arg("z"), py::arg("ys"), py::arg("rho"),
-        py::arg("mode"));
+        py::arg("mode"), py::arg("x0s") = std::vector<at::Tensor>(),
+        py::arg("yhat0s") = std::vector<at::Tensor>(),
+        py::arg("rho_used") = std::vector<double>());
   m.def("cross_entropy_fwd", &fedkit_cross_entropy_fwd,
         "fused log-softmax + NLL (mean): returns (loss, lse)");
   m.def("cross_entropy_bwd", &fedkit_cross_entropy_bwd, "CE backward");

@@ -271,31 +271,11 @@ class ConsensusADMM(Strategy):
             return None
         return {"z": state["z"], "y": state["y"][ck], "rho": state["rho"]}
 
-    def _bb_update(self, comm, state, x, round_idx):
-        """Replicated deterministic BB rho chain (consensus_multi.py:241-278)."""
+    def _bb_rho_chain(self, comm, state, rows, round_idx):
+        """Replicated deterministic BB rho chain (consensus_multi.py:241-278)
+        over the gathered [K, 6] statistics; sets state["rho"] and returns
+        the rho each client's turn saw."""
         bb = self.bb
-        z = state["z"]
-        if round_idx == 0:
-            for ck in comm.my_clients:
-                state["x0"][ck] = x[ck].clone()
-            return
-        if round_idx % bb.period_T != 0:
-            return
-        # per-client scalars: a = y - yhat0, b = x - z, dx = x - x0
-        per_client = {}
-        for ck in comm.my_clients:
-            if native_enabled(z):
-                # one fused pass over the five vectors, one host sync
-                per_client[ck] = consensus.bb_stats(
-                    state["y"][ck], state["yhat0"][ck], x[ck], z,
-                    state["x0"][ck]).tolist()
-                continue
-            a = state["y"][ck] - state["yhat0"][ck]
-            b = x[ck] - z
-            dx = x[ck] - state["x0"][ck]
-            per_client[ck] = [float(a.dot(a)), float(a.dot(b)), float(b.dot(b)),
-                              float(a.dot(dx)), float(b.dot(dx)), float(dx.dot(dx))]
-        rows = comm.gather_scalar_rows(per_client)   # [K, 6] on every rank
         rho = state["rho"]
         rho_used = [0.0] * comm.K
         for ck in range(comm.K):
@@ -319,24 +299,76 @@ class ConsensusADMM(Strategy):
                     print('admm %d alphas=(%e,%e,%e)' % (round_idx, alpha, alphaSD, alphaMG))
             rho = rhonew
         state["rho"] = rho
+        return rho_used
+
+    def _bb_update(self, comm, state, x, round_idx):
+        """BB statistics, rho chain and carry, one client at a time."""
+        bb = self.bb
+        z = state["z"]
+        if round_idx == 0:
+            for ck in comm.my_clients:
+                state["x0"][ck] = x[ck].clone()
+            return
+        if round_idx % bb.period_T != 0:
+            return
+        # per-client scalars: a = y - yhat0, b = x - z, dx = x - x0
+        per_client = {}
+        for ck in comm.my_clients:
+            if native_enabled(z):
+                # one fused pass over the five vectors, one host sync
+                per_client[ck] = consensus.bb_stats(
+                    state["y"][ck], state["yhat0"][ck], x[ck], z,
+                    state["x0"][ck]).tolist()
+                continue
+            a = state["y"][ck] - state["yhat0"][ck]
+            b = x[ck] - z
+            dx = x[ck] - state["x0"][ck]
+            per_client[ck] = [float(a.dot(a)), float(a.dot(b)), float(b.dot(b)),
+                              float(a.dot(dx)), float(b.dot(dx)), float(dx.dot(dx))]
+        rows = comm.gather_scalar_rows(per_client)   # [K, 6] on every rank
+        rho_used = self._bb_rho_chain(comm, state, rows, round_idx)
         # carry forward own client's yhat/x0 with the rho seen at its turn
         for ck in comm.my_clients:
             state["yhat0"][ck] = state["y"][ck] + rho_used[ck] * (x[ck] - z)
             state["x0"][ck] = x[ck].clone()
 
+    def _bb_fused(self, comm, state, x, cks, round_idx) -> dict:
+        """BB for a fused round: the statistics of all clients in one pass
+        and ONE host read, the same rho chain, and the carry left to
+        aggregate_round, as the keyword arguments this returns (it writes
+        yhat0 / x0 in place from the operands it reads anyway)."""
+        x0s = [state["x0"][ck] for ck in cks]
+        if round_idx == 0:
+            return {"x0s": x0s}
+        if round_idx % self.bb.period_T != 0:
+            return {}
+        yhat0s = [state["yhat0"][ck] for ck in cks]
+        stats = consensus.bb_stats_round(
+            [state["y"][ck] for ck in cks], yhat0s, [x[ck] for ck in cks],
+            state["z"], x0s).tolist()
+        rows = comm.gather_scalar_rows(dict(zip(cks, stats)))
+        rho_used = self._bb_rho_chain(comm, state, rows, round_idx)
+        return {"x0s": x0s, "yhat0s": yhat0s,
+                "rho_used": [rho_used[ck] for ck in cks]}
+
     def aggregate(self, comm, state, x, round_idx):
         N = state["N"]
+        fused = self._fused_round(comm, state, x)
+        cks = sorted(x)
+        carry = {}
         if self.bb.enabled:
-            self._bb_update(comm, state, x, round_idx)
+            if fused:
+                carry = self._bb_fused(comm, state, x, cks, round_idx)
+            else:
+                self._bb_update(comm, state, x, round_idx)
         rho = state["rho"]
         z = state["z"]
-        if self._fused_round(comm, state, x):
-            # z-update, every dual update and the 1 + K squared residual
-            # norms in one pass, then ONE host read
-            cks = sorted(x)
+        if fused:
+            # z-update, every dual update, the BB carry and the 1 + K squared
+            # residual norms in one pass, then ONE host read
             znew, res = consensus.aggregate_round(
                 [x[ck] for ck in cks], z, [state["y"][ck] for ck in cks],
-                rho=rho, mode="admm")
+                rho=rho, mode="admm", **carry)
             state["z"] = znew
             sq = res.tolist()
             rows = comm.gather_scalar_rows(

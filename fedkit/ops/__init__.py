@@ -13,7 +13,9 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
   penalty_fwd / penalty_bwd      fused FedProx/ADMM penalty + L1/L2 regulariser
   admm_dual_update / bb_stats    fused ADMM y-update and BB inner products
   aggregate_round                one-pass K-client round: z-update, dual
-                                 update and residuals (FedAvg/FedProx/ADMM)
+                                 update and residuals (FedAvg/FedProx/ADMM),
+                                 optional BB carry (yhat0, x0) for ADMM
+  bb_stats_round                 BB inner products of all K clients, one pass
 
 Dispatch policy (this is the "native code is THE path that runs" rule):
   * on a ROCm GPU the HIP kernels are used; if the extension is missing the

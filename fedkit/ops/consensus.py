@@ -13,7 +13,9 @@ the block, no autograd tape over a dozen elementwise ops.  The aggregation
 side has `admm_dual_update` (y += rho (x-z) fused with the primal-residual
 norm) and `bb_stats` (the six Barzilai-Borwein inner products in one pass);
 `aggregate_round` runs a whole round of K local clients (z-update, dual
-update, residuals) as one pass over the operands.
+update, residuals) as one pass over the operands.  With adaptive rho,
+`bb_stats_round` forms the statistics of all K clients in one pass and
+`aggregate_round` writes the BB carry (yhat0, x0) from the operands it holds.
 
 All vectors are fp32 in PHYSICAL (storage) element order, the order
 flat.pack / paramvec.flat_physical use.  Dispatch follows the package rule:
@@ -122,7 +124,10 @@ MAX_FUSED_CLIENTS = 32     # kMaxClients of csrc/consensus.hip
 
 def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
                     ys: Optional[Sequence[torch.Tensor]] = None,
-                    rho: Optional[float] = None, mode: str = "fedavg"):
+                    rho: Optional[float] = None, mode: str = "fedavg",
+                    x0s: Optional[Sequence[torch.Tensor]] = None,
+                    yhat0s: Optional[Sequence[torch.Tensor]] = None,
+                    rho_used: Optional[Sequence[float]] = None):
     """One aggregation round over the K client vectors `xs` held in this
     process; returns (znew, res).
 
@@ -136,6 +141,14 @@ def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
     not modified and znew is a new tensor.  On the GPU this is one pass over
     the operands (csrc/consensus.hip, 1 <= K <= 32) whose znew and ys are
     bitwise those of the torch sequence below.
+
+    BB carry (admm only; what adaptive rho keeps from one BB round to the
+    next, written in place by the same pass, from `ys` as they came in and
+    the old `z`):
+      x0s                      x0s[k] = xs[k]   (round 0)
+      x0s, yhat0s, rho_used    also yhat0s[k] = ys[k] + rho_used[k] (xs[k] - z)
+    `rho_used` is K floats, the rho the BB chain had at client k's turn.  The
+    outputs may not overlap an operand or each other.
     """
     assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
     xs = list(xs)
@@ -144,13 +157,30 @@ def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
         assert len(ys) == len(xs), "admm needs one dual vector per client"
     if mode != "fedavg":
         assert rho is not None, f"{mode} needs rho"
+    carry = [v is not None for v in (x0s, yhat0s, rho_used)]
+    if any(carry) and mode != "admm":
+        raise ValueError("x0s / yhat0s / rho_used are admm operands")
+    if carry not in ([False] * 3, [True, False, False], [True] * 3):
+        raise ValueError("the BB carry is x0s alone, or x0s, yhat0s and "
+                         "rho_used together")
+    x0s = list(x0s) if carry[0] else []
+    yhat0s = list(yhat0s) if carry[1] else []
+    rho_used = [float(r) for r in rho_used] if carry[2] else []
     if _use_native(z):
         from . import require_ext
         znew, res = require_ext().aggregate_round(
             xs, z, ys if mode == "admm" else [],
-            0.0 if rho is None else float(rho), AGGREGATE_MODES.index(mode))
+            0.0 if rho is None else float(rho), AGGREGATE_MODES.index(mode),
+            x0s, yhat0s, rho_used)
         return znew, res
     K = len(xs)
+    if any(len(v) != K for v in (x0s, yhat0s, rho_used) if v):
+        raise ValueError(f"the BB carry needs one entry per client ({K})")
+    # ConsensusADMM._bb_update's carry, before the duals move
+    for k in range(len(yhat0s)):
+        yhat0s[k].copy_(ys[k] + rho_used[k] * (xs[k] - z))
+    for k in range(len(x0s)):
+        x0s[k].copy_(xs[k])
     contrib = [y + rho * x for x, y in zip(xs, ys)] if mode == "admm" else xs
     znew = torch.zeros_like(contrib[0])
     for c in contrib:
@@ -180,3 +210,20 @@ def bb_stats(y: torch.Tensor, yhat0: torch.Tensor, x: torch.Tensor,
     dx = x - x0
     return torch.stack([a.dot(a), a.dot(b), b.dot(b),
                         a.dot(dx), b.dot(dx), dx.dot(dx)])
+
+
+def bb_stats_round(ys: Sequence[torch.Tensor], yhat0s: Sequence[torch.Tensor],
+                   xs: Sequence[torch.Tensor], z: torch.Tensor,
+                   x0s: Sequence[torch.Tensor]) -> torch.Tensor:
+    """fp32 [K, 6] on z's device: row k is bb_stats(ys[k], yhat0s[k], xs[k],
+    z, x0s[k]), bit for bit.  On the GPU the K <= 32 clients are served by
+    one pass (csrc/consensus.hip) that reads z once per 4 clients, so a BB
+    round costs one host read instead of K."""
+    ys, yhat0s, xs, x0s = list(ys), list(yhat0s), list(xs), list(x0s)
+    if not len(ys) == len(yhat0s) == len(xs) == len(x0s) >= 1:
+        raise ValueError("bb_stats_round needs K >= 1 vectors in every list")
+    if _use_native(z):
+        from . import require_ext
+        return require_ext().bb_stats_round(ys, yhat0s, xs, z, x0s)
+    return torch.stack([bb_stats(ys[k], yhat0s[k], xs[k], z, x0s[k])
+                        for k in range(len(xs))])

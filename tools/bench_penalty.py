@@ -22,6 +22,15 @@ at its linear head's N (512*10 + 10).  Device time, and for fedprox / admm
 wall time including the host reads of the residuals (one .tolist() against
 K+1 .item() calls).
 
+Section `bb`: one adaptive-rho (BB) round of K = 10 local clients at the
+same two N.  Fused: bb_stats_round, then aggregate_round with the full
+carry.  Sequence: what ConsensusADMM ran for that round before the two
+existed: bb_stats per client, then per client `y + rho_used * (x - z)` and
+`x.clone()`, then aggregate_round.  The wall rows add the host reads (one
+.tolist() of the [K, 6] statistics against K, and the residuals' .tolist()
+on both sides); the host rho chain between the passes is the same code on
+both sides and is not timed.
+
 Method: warm-up, then SAMPLES samples per path taken alternately (fused,
 torch, fused, ...), each sample ITERS back-to-back calls between two device
 events; the reported figure is the median sample in microseconds per call.
@@ -170,11 +179,60 @@ def aggregate_section(dev, row):
                           sampler=sample_wall_us))
 
 
+def bb_section(dev, row):
+    K = AGG_K
+    rho_used = [RHO * (1 + k / 64) for k in range(K)]
+    for name, n in AGG_SIZES.items():
+        g = torch.Generator().manual_seed(3)
+        rn = lambda: (torch.randn(n, generator=g) * 0.05).to(dev)  # noqa: E731
+        xs = [rn() for _ in range(K)]
+        z = rn()
+        # each path owns its duals and carry vectors and updates them on every
+        # timed call; with constant x the duals stay finite (y_k sums to ~0)
+        own = lambda: ([torch.zeros(n, device=dev) for _ in range(K)],  # noqa: E731
+                       [rn() for _ in range(K)], [rn() for _ in range(K)])
+        ya, ha, pa = own()
+        yb, hb, pb = own()
+
+        def fused(read=False):
+            st = consensus.bb_stats_round(ya, ha, xs, z, pa)
+            if read:
+                st = st.tolist()
+            _, res = consensus.aggregate_round(
+                xs, z, ya, rho=RHO, mode="admm", x0s=pa, yhat0s=ha,
+                rho_used=rho_used)
+            return res.tolist() if read else res
+
+        def sequence(read=False):
+            for k in range(K):
+                st = consensus.bb_stats(yb[k], hb[k], xs[k], z, pb[k])
+                if read:
+                    st = st.tolist()
+            for k in range(K):
+                hb[k] = yb[k] + rho_used[k] * (xs[k] - z)
+                pb[k] = xs[k].clone()
+            _, res = consensus.aggregate_round(xs, z, yb, rho=RHO,
+                                               mode="admm")
+            return res.tolist() if read else res
+
+        # same numbers first: one round of each path from the same state
+        fused()
+        sequence()
+        same = all(torch.equal(a, b) for a, b in zip(ya + ha + pa,
+                                                      yb + hb + pb))
+        print(f"{name} bb: y, yhat0, x0 of the two paths equal: {same}",
+              flush=True)
+        row(f"{name}: BB round K={K} (device)", n, ab(fused, sequence))
+        row(f"{name}: BB round K={K} (wall, with host reads)", n,
+            ab(lambda: fused(True), lambda: sequence(True),
+               sampler=sample_wall_us))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table here")
     ap.add_argument("--section", default="all",
-                    choices=["all", "penalty", "aggregate"])
+                    choices=["all", "penalty", "aggregate", "bb"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_penalty needs a GPU")
@@ -189,7 +247,7 @@ def main():
                      f"| {sa:.1f} / {sb:.1f} |")
         print(lines[-1], flush=True)
 
-    plists = param_lists(dev) if args.section != "aggregate" else {}
+    plists = param_lists(dev) if args.section in ("all", "penalty") else {}
     for name, params in plists.items():
         n = sum(p.numel() for p in params)
         g = torch.Generator().manual_seed(1)
@@ -254,8 +312,10 @@ def main():
         row(f"{name}: admm_dual_update (device)", n,
             ab(lambda: consensus.admm_dual_update(yy, x, z, RHO), dual_torch))
 
-    if args.section != "penalty":
+    if args.section in ("all", "aggregate"):
         aggregate_section(dev, row)
+    if args.section in ("all", "bb"):
+        bb_section(dev, row)
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
