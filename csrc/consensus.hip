@@ -29,6 +29,7 @@
 // otherwise that side falls back to four dword accesses.  Units that
 // straddle a tensor boundary or the tail take a per-element scalar path.
 
+#include "agg_common.h"
 #include "multi_tensor.h"
 
 #include <cmath>
@@ -36,48 +37,10 @@
 
 namespace {
 
+using namespace fedkit_agg;
 using fedkit_mt::DeviceGuard;
 using fedkit_mt::for_each_unit;
 using fedkit_mt::SegTable;
-
-constexpr int kBlock = 256;
-constexpr int kRedGrid = 512;   // workgroup cap of the reduction kernels
-
-typedef __attribute__((ext_vector_type(4))) float f4;
-
-__device__ __forceinline__ bool aligned16(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
-
-__device__ __forceinline__ f4 load4(const float* p) {
-  if (aligned16(p)) return *reinterpret_cast<const f4*>(p);
-  f4 v;
-  v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
-  return v;
-}
-
-__device__ __forceinline__ void store4(float* p, f4 v) {
-  if (aligned16(p)) {
-    *reinterpret_cast<f4*>(p) = v;
-  } else {
-    p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
-  }
-}
-
-// Sum of v over the 256-thread workgroup (NW = 4 waves; 128 threads with
-// NW = 2), valid in thread 0.  Wave64 shuffle tree, then the wave sums in
-// index order: a fixed order.
-template <int NW = 4>
-__device__ __forceinline__ float block_sum(float v, float* red /* [4] */) {
-  static_assert(NW == 4 || NW == 2, "256- or 128-thread workgroups");
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_down(v, off, kWave);
-  __syncthreads();   // red may still be read from a previous call
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if constexpr (NW == 2) return red[0] + red[1];
-  else return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 template <bool HZ, bool HY>
 __device__ __forceinline__ float pen_term(float x, float z, float y,
@@ -172,10 +135,6 @@ __device__ __forceinline__ float add_rounded(float a, float b) {
   return a + b;
 }
 
-// kernels whose results are compared bit for bit: no packed fp32 ALU forms
-#define FEDKIT_AGG_KERNEL \
-  __global__ void __attribute__((target("no-packed-fp32-ops")))
-
 // y += rho (x - z);  part[blockIdx.x] = partial sum of (rho (x - z))^2
 FEDKIT_AGG_KERNEL __launch_bounds__(kBlock)
 admm_dual_update_kernel(float* __restrict__ y, const float* __restrict__ x,
@@ -253,8 +212,6 @@ bb_stats_kernel(const float* __restrict__ y, const float* __restrict__ yh,
     if (threadIdx.x == 0) part[(long long)blockIdx.x * 6 + c] = s;
   }
 }
-
-constexpr int kMaxClients = 32;
 
 // ---- BB statistics of all K local clients in one launch ----
 //
@@ -396,11 +353,6 @@ enum { kFedAvg = 0, kFedProx = 1, kAdmm = 2 };
 // (CarryArg<CARRY>), and an unnamed type in a kernel's mangled name is
 // numbered differently by the host and the device compilation
 constexpr int kCarryNone = 0, kCarryX0 = 1, kCarryFull = 2;
-
-struct ClientTable {              // by value in the kernarg segment, 512 B
-  const float* x[kMaxClients];
-  float* y[kMaxClients];
-};
 
 struct CarryTable {               // by value in the kernarg segment, 640 B
   float* x0[kMaxClients];

@@ -53,6 +53,9 @@ std::vector<at::Tensor> fedkit_aggregate_round(
     std::vector<at::Tensor> ys, double rho, int64_t mode,
     std::vector<at::Tensor> x0s, std::vector<at::Tensor> yhat0s,
     std::vector<double> rho_used);
+std::vector<at::Tensor> fedkit_robust_round(std::vector<at::Tensor> xs,
+                                            const at::Tensor& z, double rho,
+                                            int64_t mode, int64_t trim);
 
 std::vector<at::Tensor> fedkit_cross_entropy_fwd(const at::Tensor& logits,
                                                  const at::Tensor& labels);
@@ -197,6 +200,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mode"), py::arg("x0s") = std::vector<at::Tensor>(),
         py::arg("yhat0s") = std::vector<at::Tensor>(),
         py::arg("rho_used") = std::vector<double>());
+  m.def("robust_round", &fedkit_robust_round,
+        "one-pass coordinate-wise trimmed-mean / median round over K <= 32 "
+        "clients (mode 0 fedavg, 1 fedprox): per element the K values are "
+        "sorted (torch.sort's order, NaN last) and ranks trim..K-trim-1 are "
+        "averaged; returns (znew, res) as aggregate_round does",
+        py::arg("xs"), py::arg("z"), py::arg("rho"), py::arg("mode"),
+        py::arg("trim"));
   m.def("cross_entropy_fwd", &fedkit_cross_entropy_fwd,
         "fused log-softmax + NLL (mean): returns (loss, lse)");
   m.def("cross_entropy_bwd", &fedkit_cross_entropy_bwd, "CE backward");

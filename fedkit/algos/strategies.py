@@ -60,6 +60,28 @@ class Strategy:
     # sequence.  z and y come out bitwise the same; False restores the
     # sequence (FedConfig.fused_aggregate).
     fused_aggregate = True
+    # Byzantine-robust aggregation (FedAvg / FedProx): "trimmed_mean" drops
+    # floor(trim_frac * K) values at each end of every coordinate's K client
+    # values, "median" all but the middle one or two; None is the mean.
+    robust: Optional[str] = None
+    trim_frac: float = 0.1
+
+    def _set_robust(self, robust: Optional[str], trim_frac: float):
+        if robust is not None and robust not in consensus.ROBUST_RULES:
+            raise ValueError(f"unknown robust rule {robust!r}; one of "
+                             f"{consensus.ROBUST_RULES}")
+        self.robust, self.trim_frac = robust, float(trim_frac)
+
+    def _robust_round(self, comm: Communicator, state: dict, pending,
+                      rho: Optional[float], mode: str):
+        """Every rank runs the same round over the K gathered vectors: one
+        pass of consensus.robust_round (HIP on a GPU), or the torch sequence
+        that defines it when fused_aggregate is off; same z either way."""
+        trim = consensus.robust_trim(self.robust, self.trim_frac, comm.K)
+        fused = (self.fused_aggregate
+                 and comm.K <= consensus.MAX_FUSED_CLIENTS)
+        fn = consensus.robust_round if fused else consensus.robust_round_torch
+        return fn(pending(), state["z"], rho, mode, trim)
 
     def init_block(self, comm: Communicator, N: int, device,
                    x0: Optional[Dict[int, torch.Tensor]] = None,
@@ -113,7 +135,12 @@ class FedAvg(Strategy):
     name = "fedavg"
     writeback_z = True
 
+    def __init__(self, robust: Optional[str] = None, trim_frac: float = 0.1):
+        self._set_robust(robust, trim_frac)
+
     def aggregate_start(self, comm, state, x):
+        if self.robust:
+            return comm.gather_client_vectors_async(x)
         if self._fused_round(comm, state, x):
             return None     # no clones, no collective: finish() does it all
         return comm.sum_across_clients_async(
@@ -121,6 +148,11 @@ class FedAvg(Strategy):
 
     def aggregate_finish(self, comm, state, x, pending, round_idx):
         z, N = state["z"], state["N"]
+        if self.robust:
+            znew, res = self._robust_round(comm, state, pending, None,
+                                           "fedavg")
+            state["z"] = znew
+            return {"dual": torch.sqrt(res[0]) / N}
         if pending is None:
             # one pass: znew and sum (z - znew)^2, still no host sync
             znew, res = consensus.aggregate_round(
@@ -149,7 +181,9 @@ class FedProx(Strategy):
     name = "fedprox"
     uses_penalty = True
 
-    def __init__(self, rho0: float = 1.0, warmup_rounds: int = 0):
+    def __init__(self, rho0: float = 1.0, warmup_rounds: int = 0,
+                 robust: Optional[str] = None, trim_frac: float = 0.1):
+        self._set_robust(robust, trim_frac)
         self.rho0 = rho0
         # engine extension, default 0 = reference behavior (see
         # ConsensusADMM.warmup_rounds: z starts at 0 per block, so the
@@ -189,6 +223,8 @@ class FedProx(Strategy):
                 "rho": self._rho(state.get("block_idx", 0), ck)}
 
     def aggregate_start(self, comm, state, x):
+        if self.robust:
+            return comm.gather_client_vectors_async(x)
         if self._fused_round(comm, state, x):
             return None     # no clones, no collective: finish() does it all
         return comm.sum_across_clients_async(
@@ -201,6 +237,16 @@ class FedProx(Strategy):
 
     def aggregate_finish(self, comm, state, x, pending, round_idx):
         z, N, rho = state["z"], state["N"], state["rho"]
+        if self.robust:
+            # all K residuals are formed on every rank: nothing to gather
+            znew, res = self._robust_round(comm, state, pending, rho,
+                                           "fedprox")
+            sq = res.tolist()
+            state["z"] = znew
+            state["round"] = round_idx + 1
+            return {"dual": math.sqrt(sq[0]) / N,
+                    "primal": sum(math.sqrt(v) for v in sq[1:]) / N,
+                    "rho": rho}
         if pending is None:
             # one pass, then ONE host read of the 1 + K squared norms
             cks = sorted(x)

@@ -16,6 +16,9 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
                                  update and residuals (FedAvg/FedProx/ADMM),
                                  optional BB carry (yhat0, x0) for ADMM
   bb_stats_round                 BB inner products of all K clients, one pass
+  robust_round                   one-pass coordinate-wise trimmed-mean / median
+                                 round over K clients (FedAvg/FedProx), NaN-
+                                 and Inf-safe total order, with residuals
 
 Dispatch policy (this is the "native code is THE path that runs" rule):
   * on a ROCm GPU the HIP kernels are used; if the extension is missing the

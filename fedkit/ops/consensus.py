@@ -16,6 +16,9 @@ norm) and `bb_stats` (the six Barzilai-Borwein inner products in one pass);
 update, residuals) as one pass over the operands.  With adaptive rho,
 `bb_stats_round` forms the statistics of all K clients in one pass and
 `aggregate_round` writes the BB carry (yhat0, x0) from the operands it holds.
+`robust_round` is the Byzantine-robust form of a FedAvg / FedProx round: the
+coordinate-wise trimmed mean or median over the K clients in one pass
+(csrc/robust.hip).
 
 All vectors are fp32 in PHYSICAL (storage) element order, the order
 flat.pack / paramvec.flat_physical use.  Dispatch follows the package rule:
@@ -25,6 +28,7 @@ strategies have always used, in the same order, so CPU runs stay
 bit-identical.
 """
 
+import math
 from typing import Optional, Sequence
 
 import torch
@@ -194,6 +198,76 @@ def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
             if mode == "admm":
                 ys[k].add_(ydelta)
     return znew, torch.stack(res)
+
+
+ROBUST_RULES = ("trimmed_mean", "median")
+
+
+def robust_trim(rule: str, trim_frac: float, K: int) -> int:
+    """Ranks dropped at each end: floor(trim_frac * K) for "trimmed_mean",
+    (K - 1) // 2 for "median" (the middle value for odd K, the mean of the
+    two middle values for even K)."""
+    if rule not in ROBUST_RULES:
+        raise ValueError(f"unknown robust rule {rule!r}; one of {ROBUST_RULES}")
+    trim = (K - 1) // 2 if rule == "median" else math.floor(trim_frac * K)
+    if not 0 <= 2 * trim < K:
+        raise ValueError(f"trim_frac {trim_frac} drops {2 * trim} of {K} "
+                         "clients; it must leave at least one")
+    return trim
+
+
+def robust_round_torch(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                       rho: Optional[float] = None, mode: str = "fedavg",
+                       trim: int = 0):
+    """The torch sequence that defines `robust_round` bit for bit, on the
+    operands' device and in their dtype."""
+    K, m = len(xs), len(xs) - 2 * trim
+    s = torch.sort(torch.stack(list(xs)), dim=0).values
+    znew = torch.zeros_like(z)
+    for r in range(trim, K - trim):
+        znew += s[r]
+    znew /= m
+    res = [torch.norm(z - znew) ** 2]
+    if mode != "fedavg":
+        res += [torch.norm(rho * (x - znew)) ** 2 for x in xs]
+    return znew, torch.stack(res)
+
+
+def robust_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                 rho: Optional[float] = None, mode: str = "fedavg",
+                 trim: int = 0):
+    """One Byzantine-robust aggregation round over the K client vectors
+    `xs`: the coordinate-wise trimmed mean (Yin et al., 2018).  Per element
+    the K values are sorted ascending in torch.sort's order (-inf < finite <
+    +inf < NaN), the `trim` smallest and `trim` largest are dropped
+    (0 <= 2 * trim < K) and the other m = K - 2 * trim are averaged;
+    trim = (K - 1) // 2 is the median.  Up to `trim` clients may hold
+    anything, NaN and Inf included, and znew stays within the range of the
+    others.
+
+    Returns (znew, res) as `aggregate_round` does: res[0] = sum (z - znew)^2
+    and, in fedprox mode, res[1 + k] = sum (rho (xs[k] - znew))^2 (NaN for a
+    NaN client: that is the signal).  Modes are fedavg and fedprox; there is
+    no robust ADMM round.  On the GPU this is one pass over the operands
+    (csrc/robust.hip, 1 <= K <= 32), with znew bitwise that of
+    `robust_round_torch`, which is the CPU path.
+    """
+    if mode == "admm":
+        raise ValueError("there is no robust ADMM round; use fedavg or fedprox")
+    assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+    xs = list(xs)
+    if mode != "fedavg":
+        assert rho is not None, f"{mode} needs rho"
+    if _use_native(z):
+        from . import require_ext
+        znew, res = require_ext().robust_round(
+            xs, z, 0.0 if rho is None else float(rho),
+            AGGREGATE_MODES.index(mode), int(trim))
+        return znew, res
+    if not 1 <= len(xs) or not 0 <= 2 * trim < len(xs):
+        raise ValueError(f"robust_round needs 0 <= 2 * trim < K, got trim "
+                         f"{trim} for {len(xs)} clients")
+    return robust_round_torch(xs, z, rho, mode, trim)
 
 
 def bb_stats(y: torch.Tensor, yhat0: torch.Tensor, x: torch.Tensor,

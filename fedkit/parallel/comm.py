@@ -62,6 +62,24 @@ class Communicator:
         """
         raise NotImplementedError
 
+    def gather_client_vectors(self, per_client: Dict[int, torch.Tensor]
+                              ) -> List[torch.Tensor]:
+        """The K client vectors in client order, on every rank.
+
+        Order statistics (trimmed mean, median) cannot travel through a sum
+        all-reduce; every rank gathers the K vectors and runs the same
+        deterministic robust round over them.  LocalComm: the inputs.
+        DistComm: one all-gather into a [K, N] buffer, returned as its rows.
+        """
+        raise NotImplementedError
+
+    def gather_client_vectors_async(self, per_client: Dict[int, torch.Tensor]):
+        """Launch the gather; returns wait() -> the K vectors (DistComm: on
+        the comm stream, as sum_across_clients_async).  Default: synchronous.
+        """
+        out = self.gather_client_vectors(per_client)
+        return lambda: out
+
     def gather_scalar_rows(self, per_client: Dict[int, List[float]]) -> torch.Tensor:
         """All-gather one row of scalars per client -> [K, n] fp64 on CPU."""
         raise NotImplementedError
@@ -92,6 +110,10 @@ class LocalComm(Communicator):
         for ck in sorted(per_client):
             total += per_client[ck]
         return total
+
+    def gather_client_vectors(self, per_client):
+        assert len(per_client) == self.K
+        return [per_client[ck] for ck in sorted(per_client)]
 
     def gather_scalar_rows(self, per_client):
         rows = [per_client[ck] for ck in sorted(per_client)]
@@ -171,6 +193,30 @@ class DistComm(Communicator):
         def wait():
             work.wait()
             return vec
+        return wait
+
+    def gather_client_vectors(self, per_client):
+        return self.gather_client_vectors_async(per_client)()
+
+    def gather_client_vectors_async(self, per_client):
+        assert list(per_client.keys()) == self.my_clients
+        vec = per_client[self.rank].contiguous().view(-1)
+        # flat [K * N]: gloo's all-gather wants input and output of one rank
+        buf = vec.new_empty(self.K * vec.numel())
+        if self.comm_stream is not None:
+            ev = torch.cuda.Event()
+            ev.record()
+            with torch.cuda.stream(self.comm_stream):
+                self.comm_stream.wait_event(ev)
+                work = dist.all_gather_into_tensor(buf, vec, async_op=True)
+            vec.record_stream(self.comm_stream)
+            buf.record_stream(self.comm_stream)
+        else:
+            work = dist.all_gather_into_tensor(buf, vec, async_op=True)
+
+        def wait():
+            work.wait()      # GPU: fences the CURRENT (compute) stream
+            return list(buf.view(self.K, -1).unbind(0))
         return wait
 
     def gather_scalar_rows(self, per_client):

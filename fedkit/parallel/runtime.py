@@ -110,6 +110,11 @@ class FedConfig:
                                        # K <= 32: the aggregation round as
                                        # one fused HIP pass (False = the
                                        # torch sequence; same z and y bits)
+    robust_agg: str = "none"           # none | trimmed_mean | median: the
+                                       # coordinate-wise robust rule of a
+                                       # FedAvg / FedProx round (none = mean)
+    trim_frac: float = 0.1             # trimmed_mean drops floor(trim_frac*K)
+                                       # client values at each end
 
     def model_name(self) -> str:
         if self.model:
@@ -122,14 +127,20 @@ class FedConfig:
         return strategy
 
     def _make_strategy(self) -> Strategy:
+        robust = dict(robust=None if self.robust_agg == "none"
+                      else self.robust_agg, trim_frac=self.trim_frac)
         if self.strategy == "none":
             return NoConsensus()
         if self.strategy == "fedavg":
-            return FedAvg()
+            return FedAvg(**robust)
         if self.strategy == "fedprox":
             return FedProx(rho0=self.admm_rho0,
-                           warmup_rounds=self.penalty_warmup_rounds)
+                           warmup_rounds=self.penalty_warmup_rounds, **robust)
         if self.strategy == "admm":
+            if robust["robust"] is not None:
+                raise ValueError(
+                    "robust_agg needs strategy fedavg or fedprox: there is "
+                    "no robust ADMM round")
             bb = BBConfig(self.bb_update, self.bb_period_T,
                           self.bb_alphacorrmin, self.bb_epsilon, self.bb_rhomax)
             return ConsensusADMM(rho0=self.admm_rho0, bb=bb,

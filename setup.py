@@ -19,6 +19,7 @@ SOURCES = [
     "csrc/elementwise.hip",
     "csrc/flat_ops.hip",
     "csrc/consensus.hip",
+    "csrc/robust.hip",
     "csrc/loss.hip",
     "csrc/losses_extra.hip",
     "csrc/linear.hip",

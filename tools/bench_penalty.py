@@ -31,6 +31,13 @@ existed: bb_stats per client, then per client `y + rho_used * (x - z)` and
 on both sides); the host rho chain between the passes is the same code on
 both sides and is not timed.
 
+Section `robust`: one robust round of K = 10 local clients at the same two
+N, consensus.robust_round (csrc/robust.hip) against the torch sequence that
+defines it (stack, sort along the client axis, adds in rank order, divide,
+norms), for fedavg / fedprox with trim = 1 and the median.  A further row
+per mode times it against the plain mean of aggregate_round at the same K
+and N (the same bytes read): the price of robustness.  Device time.
+
 Method: warm-up, then SAMPLES samples per path taken alternately (fused,
 torch, fused, ...), each sample ITERS back-to-back calls between two device
 events; the reported figure is the median sample in microseconds per call.
@@ -228,11 +235,39 @@ def bb_section(dev, row):
                sampler=sample_wall_us))
 
 
+def robust_section(dev, row):
+    for name, n in AGG_SIZES.items():
+        g = torch.Generator().manual_seed(4)
+        xs = [(torch.randn(n, generator=g) * 0.05).to(dev)
+              for _ in range(AGG_K)]
+        z = (torch.randn(n, generator=g) * 0.05).to(dev)
+        for mode in ("fedavg", "fedprox"):
+            for label, trim in (("trim=1", 1), ("median", (AGG_K - 1) // 2)):
+                def fused(trim=trim):
+                    return consensus.robust_round(xs, z, RHO, mode, trim)
+
+                def sequence(trim=trim):
+                    return consensus.robust_round_torch(xs, z, RHO, mode,
+                                                        trim)
+
+                same = torch.equal(fused()[0], sequence()[0])
+                print(f"{name} robust {mode} {label}: znew of the two paths "
+                      f"equal: {same}", flush=True)
+                row(f"{name}: robust {mode} {label} K={AGG_K} (device)", n,
+                    ab(fused, sequence))
+            row(f"{name}: robust {mode} trim=1 vs plain mean K={AGG_K} "
+                "(device; columns: robust, mean, mean/robust)", n,
+                ab(lambda: consensus.robust_round(xs, z, RHO, mode, 1),
+                   lambda: consensus.aggregate_round(xs, z, rho=RHO,
+                                                     mode=mode)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table here")
     ap.add_argument("--section", default="all",
-                    choices=["all", "penalty", "aggregate", "bb"])
+                    choices=["all", "penalty", "aggregate", "bb",
+                             "robust"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_penalty needs a GPU")
@@ -316,6 +351,8 @@ def main():
         aggregate_section(dev, row)
     if args.section in ("all", "bb"):
         bb_section(dev, row)
+    if args.section in ("all", "robust"):
+        robust_section(dev, row)
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
