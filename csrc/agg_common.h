@@ -1,6 +1,7 @@
-// Shared by the aggregation kernels (consensus.hip, robust.hip): the client
-// table, the aligned 16-byte accessors, the workgroup sum and the attribute
-// of kernels whose results are compared bit for bit.
+// Shared by the aggregation kernels (consensus.hip, robust.hip, krum.hip):
+// the client table, the aligned 16-byte and unit-wide accessors, the
+// workgroup sum and the attribute of kernels whose results are compared bit
+// for bit.
 #pragma once
 
 #include "fedkit_common.h"
@@ -39,6 +40,30 @@ __device__ __forceinline__ void store4(float* p, f4 v) {
   } else {
     p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
   }
+}
+
+template <int V>
+using fv = float __attribute__((ext_vector_type(V)));
+
+// V consecutive floats at p; one load where p is aligned to the unit
+template <int V>
+__device__ __forceinline__ fv<V> loadv(const float* p) {
+  if ((reinterpret_cast<uintptr_t>(p) & (4 * V - 1)) == 0)
+    return *reinterpret_cast<const fv<V>*>(p);
+  fv<V> v;
+#pragma unroll
+  for (int e = 0; e < V; ++e) v[e] = p[e];
+  return v;
+}
+
+template <int V>
+__device__ __forceinline__ void storev(float* p, fv<V> v) {
+  if ((reinterpret_cast<uintptr_t>(p) & (4 * V - 1)) == 0) {
+    *reinterpret_cast<fv<V>*>(p) = v;
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < V; ++e) p[e] = v[e];
 }
 
 // Sum of v over the 256-thread workgroup (NW = 4 waves; 128 threads with

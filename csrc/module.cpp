@@ -56,6 +56,12 @@ std::vector<at::Tensor> fedkit_aggregate_round(
 std::vector<at::Tensor> fedkit_robust_round(std::vector<at::Tensor> xs,
                                             const at::Tensor& z, double rho,
                                             int64_t mode, int64_t trim);
+at::Tensor fedkit_pairwise_sqdist(std::vector<at::Tensor> xs,
+                                  const at::Tensor& center);
+std::vector<at::Tensor> fedkit_krum_round(std::vector<at::Tensor> xs,
+                                          const at::Tensor& z,
+                                          const at::Tensor& center, double rho,
+                                          int64_t mode, int64_t f, int64_t m);
 
 std::vector<at::Tensor> fedkit_cross_entropy_fwd(const at::Tensor& logits,
                                                  const at::Tensor& labels);
@@ -207,6 +213,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "averaged; returns (znew, res) as aggregate_round does",
         py::arg("xs"), py::arg("z"), py::arg("rho"), py::arg("mode"),
         py::arg("trim"));
+  m.def("pairwise_sqdist", &fedkit_pairwise_sqdist,
+        "squared distances between K <= 32 vectors from the MFMA Gram matrix "
+        "of xs[k] - center -> device fp32 [K, K], exactly symmetric, zero "
+        "diagonal, non-finite entries +inf",
+        py::arg("xs"), py::arg("center"));
+  m.def("krum_round", &fedkit_krum_round,
+        "Krum / Multi-Krum round over K <= 32 clients (mode 0 fedavg, 1 "
+        "fedprox): scores from the K - f - 2 nearest distances, the m lowest "
+        "scored clients averaged; returns (znew, res, sel int32 [K], D, "
+        "scores) with res as aggregate_round's",
+        py::arg("xs"), py::arg("z"), py::arg("center"), py::arg("rho"),
+        py::arg("mode"), py::arg("f"), py::arg("m"));
   m.def("cross_entropy_fwd", &fedkit_cross_entropy_fwd,
         "fused log-softmax + NLL (mean): returns (loss, lse)");
   m.def("cross_entropy_bwd", &fedkit_cross_entropy_bwd, "CE backward");

@@ -53,9 +53,6 @@ using namespace fedkit_agg;
 
 enum { kFedAvg = 0, kFedProx = 1, kAdmm = 2 };   // aggregate_round's modes
 
-template <int V>
-using fv = float __attribute__((ext_vector_type(V)));
-
 __device__ __forceinline__ unsigned key_of(float v) {
   const unsigned b = __float_as_uint(v);
   if ((b & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
@@ -111,27 +108,6 @@ struct Sorter {
     run(key, std::make_index_sequence<net.n>());
   }
 };
-
-// V consecutive floats at p; one load where p is aligned to the unit
-template <int V>
-__device__ __forceinline__ fv<V> loadv(const float* p) {
-  if ((reinterpret_cast<uintptr_t>(p) & (4 * V - 1)) == 0)
-    return *reinterpret_cast<const fv<V>*>(p);
-  fv<V> v;
-#pragma unroll
-  for (int e = 0; e < V; ++e) v[e] = p[e];
-  return v;
-}
-
-template <int V>
-__device__ __forceinline__ void storev(float* p, fv<V> v) {
-  if ((reinterpret_cast<uintptr_t>(p) & (4 * V - 1)) == 0) {
-    *reinterpret_cast<fv<V>*>(p) = v;
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < V; ++e) p[e] = v[e];
-}
 
 // One unit of V elements at i0: znew, and this thread's residual sums.
 template <int NET, int V, bool PROX>

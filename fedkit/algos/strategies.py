@@ -62,7 +62,10 @@ class Strategy:
     fused_aggregate = True
     # Byzantine-robust aggregation (FedAvg / FedProx): "trimmed_mean" drops
     # floor(trim_frac * K) values at each end of every coordinate's K client
-    # values, "median" all but the middle one or two; None is the mean.
+    # values, "median" all but the middle one or two; "krum" keeps the one
+    # client closest to its K - f - 2 nearest neighbours and "multi_krum"
+    # averages the K - f best such, f = floor(trim_frac * K); None is the
+    # mean.
     robust: Optional[str] = None
     trim_frac: float = 0.1
 
@@ -76,10 +79,22 @@ class Strategy:
                       rho: Optional[float], mode: str):
         """Every rank runs the same round over the K gathered vectors: one
         pass of consensus.robust_round (HIP on a GPU), or the torch sequence
-        that defines it when fused_aggregate is off; same z either way."""
-        trim = consensus.robust_trim(self.robust, self.trim_frac, comm.K)
+        that defines it when fused_aggregate is off; same z either way.  The
+        Krum rules leave their selection in state["krum_selected"]."""
         fused = (self.fused_aggregate
                  and comm.K <= consensus.MAX_FUSED_CLIENTS)
+        if self.robust in consensus.KRUM_RULES:
+            f, m = consensus.krum_params(self.robust, self.trim_frac, comm.K)
+            if fused:
+                znew, res, sel = consensus.krum_round(
+                    pending(), state["z"], rho, mode, f, m,
+                    center=state["z"])
+            else:
+                znew, res, sel = consensus.krum_round_torch(
+                    pending(), state["z"], rho, mode, f, m)
+            state["krum_selected"] = sel
+            return znew, res
+        trim = consensus.robust_trim(self.robust, self.trim_frac, comm.K)
         fn = consensus.robust_round if fused else consensus.robust_round_torch
         return fn(pending(), state["z"], rho, mode, trim)
 

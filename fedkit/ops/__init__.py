@@ -19,6 +19,10 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
   robust_round                   one-pass coordinate-wise trimmed-mean / median
                                  round over K clients (FedAvg/FedProx), NaN-
                                  and Inf-safe total order, with residuals
+  pairwise_sqdist / krum_round   Krum / Multi-Krum round over K clients: MFMA
+                                 Gram pass over the centred vectors, on-device
+                                 scoring and selection, mean of the selected
+                                 clients with residuals (FedAvg/FedProx)
 
 Dispatch policy (this is the "native code is THE path that runs" rule):
   * on a ROCm GPU the HIP kernels are used; if the extension is missing the

@@ -18,7 +18,10 @@ update, residuals) as one pass over the operands.  With adaptive rho,
 `aggregate_round` writes the BB carry (yhat0, x0) from the operands it holds.
 `robust_round` is the Byzantine-robust form of a FedAvg / FedProx round: the
 coordinate-wise trimmed mean or median over the K clients in one pass
-(csrc/robust.hip).
+(csrc/robust.hip).  `krum_round` is the distance-based form (Krum /
+Multi-Krum): `pairwise_sqdist` from an MFMA Gram pass over the centred
+vectors, the selection on the device, and the mean of the selected clients
+(csrc/krum.hip).
 
 All vectors are fp32 in PHYSICAL (storage) element order, the order
 flat.pack / paramvec.flat_physical use.  Dispatch follows the package rule:
@@ -200,15 +203,16 @@ def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
     return znew, torch.stack(res)
 
 
-ROBUST_RULES = ("trimmed_mean", "median")
+KRUM_RULES = ("krum", "multi_krum")
+ROBUST_RULES = ("trimmed_mean", "median") + KRUM_RULES
 
 
 def robust_trim(rule: str, trim_frac: float, K: int) -> int:
     """Ranks dropped at each end: floor(trim_frac * K) for "trimmed_mean",
     (K - 1) // 2 for "median" (the middle value for odd K, the mean of the
     two middle values for even K)."""
-    if rule not in ROBUST_RULES:
-        raise ValueError(f"unknown robust rule {rule!r}; one of {ROBUST_RULES}")
+    if rule not in ("trimmed_mean", "median"):
+        raise ValueError(f"{rule!r} is not a coordinate-wise robust rule")
     trim = (K - 1) // 2 if rule == "median" else math.floor(trim_frac * K)
     if not 0 <= 2 * trim < K:
         raise ValueError(f"trim_frac {trim_frac} drops {2 * trim} of {K} "
@@ -268,6 +272,119 @@ def robust_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
         raise ValueError(f"robust_round needs 0 <= 2 * trim < K, got trim "
                          f"{trim} for {len(xs)} clients")
     return robust_round_torch(xs, z, rho, mode, trim)
+
+
+def krum_params(rule: str, trim_frac: float, K: int):
+    """(f, m) of a Krum round: f = floor(trim_frac * K) clients may be bad
+    (the `trim_frac` knob read as that fraction); "krum" averages m = 1
+    client, "multi_krum" m = K - f."""
+    if rule not in KRUM_RULES:
+        raise ValueError(f"unknown Krum rule {rule!r}; one of {KRUM_RULES}")
+    f = math.floor(trim_frac * K)
+    if K - f - 2 < 1:
+        raise ValueError(f"Krum scores need K - f - 2 >= 1 neighbours; "
+                         f"trim_frac {trim_frac} gives f = {f} of K = {K}")
+    return f, (1 if rule == "krum" else K - f)
+
+
+def _check_krum(K: int, f: int, m: int, mode: str):
+    if mode == "admm":
+        raise ValueError("there is no robust ADMM round; use fedavg or fedprox")
+    assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+    if f < 0 or K - f - 2 < 1 or not 1 <= m <= K:
+        raise ValueError(f"krum_round needs f >= 0, K - f - 2 >= 1 and "
+                         f"1 <= m <= K, got K = {K}, f = {f}, m = {m}")
+
+
+def _pairwise_sqdist_torch(xs):
+    K = len(xs)
+    d = {(i, j): ((xs[i] - xs[j]) ** 2).sum()
+         for i in range(K) for j in range(i + 1, K)}
+    d.update({(i, i): xs[0].new_zeros(()) for i in range(K)})
+    D = torch.stack([d[min(i, j), max(i, j)]
+                     for i in range(K) for j in range(K)]).reshape(K, K)
+    return torch.where(D.isfinite(), D, torch.full_like(D, math.inf))
+
+
+def pairwise_sqdist(xs: Sequence[torch.Tensor],
+                    center: torch.Tensor) -> torch.Tensor:
+    """[K, K] squared distances D_ij = sum (xs[i] - xs[j])^2, exactly
+    symmetric with a zero diagonal; a non-finite entry counts as +inf.  On
+    the GPU (fp32, 1 <= K <= 32) D_ij = G_ii + G_jj - 2 G_ij from one MFMA
+    Gram pass over xs[k] - center (csrc/krum.hip): the error scales with
+    ||xs[i] - center||^2 + ||xs[j] - center||^2, so `center` should be
+    close to the clients (the old consensus is).  The CPU forms D from the
+    differences, in the operands' dtype, and does not read `center`."""
+    xs = list(xs)
+    if _use_native(center):
+        from . import require_ext
+        return require_ext().pairwise_sqdist(xs, center)
+    return _pairwise_sqdist_torch(xs)
+
+
+def krum_round_torch(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                     rho: Optional[float] = None, mode: str = "fedavg",
+                     f: int = 0, m: Optional[int] = None):
+    """The torch sequence that defines `krum_round`, on the operands' device
+    and in their dtype; returns (znew, res, sel)."""
+    xs = list(xs)
+    K = len(xs)
+    m = K - f if m is None else m
+    _check_krum(K, f, m, mode)
+    D = _pairwise_sqdist_torch(xs)
+    D.fill_diagonal_(math.inf)          # D_ii is excluded
+    near = torch.sort(D, dim=1, stable=True).values
+    score = torch.zeros_like(near[:, 0])
+    for r in range(K - f - 2):          # ascending order
+        score += near[:, r]
+    order = torch.argsort(score, stable=True)
+    sel = torch.zeros(K, dtype=torch.bool, device=z.device)
+    sel[order[:m]] = True
+    znew = torch.zeros_like(z)
+    for k in order[:m].sort().values.tolist():
+        znew += xs[k]
+    znew /= m
+    res = [torch.norm(z - znew) ** 2]
+    if mode != "fedavg":
+        res += [torch.norm(rho * (x - znew)) ** 2 for x in xs]
+    return znew, torch.stack(res), sel
+
+
+def krum_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
+               rho: Optional[float] = None, mode: str = "fedavg", f: int = 0,
+               m: Optional[int] = None, center: Optional[torch.Tensor] = None):
+    """One Krum / Multi-Krum aggregation round (Blanchard et al., 2017) over
+    the K client vectors `xs`, of which up to `f` may be Byzantine: client i
+    is scored by the sum of its K - f - 2 smallest squared distances to the
+    other clients, and the `m` clients of lowest score (ties to the lower
+    index; m = None means K - f, m = 1 is Krum) are averaged in ascending
+    client order.  Unlike the coordinate-wise rules this rejects a client
+    whose every coordinate is in range while the vector as a whole is not.
+
+    Returns (znew, res, sel): znew and res as `robust_round` (res[1 + k] for
+    all K clients in fedprox mode, NaN for a NaN client), sel a bool [K]
+    tensor on z's device, formed without a host sync.  Needs f >= 0,
+    K - f - 2 >= 1 and 1 <= m <= K; modes are fedavg and fedprox.  On the
+    GPU (csrc/krum.hip, K <= 32) the distances come from `pairwise_sqdist`
+    around `center` (None means z) and znew is bitwise that of
+    `krum_round_torch`, the CPU path, over the same selection.
+    """
+    xs = list(xs)
+    m = len(xs) - f if m is None else m
+    if mode != "fedavg" and mode != "admm":
+        assert rho is not None, f"{mode} needs rho"
+    if _use_native(z):
+        if mode == "admm":
+            raise ValueError("there is no robust ADMM round; use fedavg or "
+                             "fedprox")
+        assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+        from . import require_ext
+        znew, res, sel, _, _ = require_ext().krum_round(
+            xs, z, z if center is None else center,
+            0.0 if rho is None else float(rho), AGGREGATE_MODES.index(mode),
+            int(f), int(m))
+        return znew, res, sel.bool()
+    return krum_round_torch(xs, z, rho, mode, f, m)
 
 
 def bb_stats(y: torch.Tensor, yhat0: torch.Tensor, x: torch.Tensor,

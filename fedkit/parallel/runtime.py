@@ -110,11 +110,14 @@ class FedConfig:
                                        # K <= 32: the aggregation round as
                                        # one fused HIP pass (False = the
                                        # torch sequence; same z and y bits)
-    robust_agg: str = "none"           # none | trimmed_mean | median: the
-                                       # coordinate-wise robust rule of a
+    robust_agg: str = "none"           # none | trimmed_mean | median (the
+                                       # coordinate-wise rules) | krum |
+                                       # multi_krum (distance-based) of a
                                        # FedAvg / FedProx round (none = mean)
     trim_frac: float = 0.1             # trimmed_mean drops floor(trim_frac*K)
-                                       # client values at each end
+                                       # client values at each end; the Krum
+                                       # rules take f = floor(trim_frac*K)
+                                       # as the number of bad clients
 
     def model_name(self) -> str:
         if self.model:

@@ -20,6 +20,7 @@ SOURCES = [
     "csrc/flat_ops.hip",
     "csrc/consensus.hip",
     "csrc/robust.hip",
+    "csrc/krum.hip",
     "csrc/loss.hip",
     "csrc/losses_extra.hip",
     "csrc/linear.hip",

@@ -38,6 +38,14 @@ norms), for fedavg / fedprox with trim = 1 and the median.  A further row
 per mode times it against the plain mean of aggregate_round at the same K
 and N (the same bytes read): the price of robustness.  Device time.
 
+Section `krum`: one Multi-Krum round (f = K // 5, m = K - f) at K = 10 and
+K = 32, N of the ResNet18 last conv block, fedavg / fedprox:
+consensus.krum_round (csrc/krum.hip) against krum_round_torch on the GPU
+(K (K - 1) / 2 difference reductions and a host read of the selection), and
+further rows against robust_round (trim = f) and the plain mean of
+aggregate_round at the same K and N.  Device time; the torch sequence is
+timed by the wall clock, since it reads the selection on the host.
+
 Method: warm-up, then SAMPLES samples per path taken alternately (fused,
 torch, fused, ...), each sample ITERS back-to-back calls between two device
 events; the reported figure is the median sample in microseconds per call.
@@ -262,12 +270,47 @@ def robust_section(dev, row):
                                                      mode=mode)))
 
 
+def krum_section(dev, row):
+    name, n = "ResNet18 last conv block", AGG_SIZES["ResNet18 last conv block"]
+    for K in (10, 32):
+        g = torch.Generator().manual_seed(5)
+        z = (torch.randn(n, generator=g) * 0.05).to(dev)
+        xs = [z + (torch.randn(n, generator=g) * 0.01).to(dev)
+              for _ in range(K)]
+        f = K // 5
+        for mode in ("fedavg", "fedprox"):
+            def fused():
+                return consensus.krum_round(xs, z, RHO, mode, f)
+
+            def sequence():
+                return consensus.krum_round_torch(xs, z, RHO, mode, f)
+
+            (za, _, sa), (zb, _, sb) = fused(), sequence()
+            print(f"{name} krum {mode} K={K}: selection equal "
+                  f"{torch.equal(sa, sb)}, znew equal {torch.equal(za, zb)}",
+                  flush=True)
+            row(f"{name}: multi_krum {mode} K={K} f={f} (wall)", n,
+                ab(fused, sequence, sampler=sample_wall_us))
+            row(f"{name}: multi_krum {mode} vs robust trim={f} K={K} "
+                "(device; columns: krum, robust, robust/krum)", n,
+                ab(fused,
+                   lambda: consensus.robust_round(xs, z, RHO, mode, f)))
+            row(f"{name}: multi_krum {mode} vs plain mean K={K} "
+                "(device; columns: krum, mean, mean/krum)", n,
+                ab(fused, lambda: consensus.aggregate_round(xs, z, rho=RHO,
+                                                            mode=mode)))
+        row(f"{name}: pairwise_sqdist K={K} vs fp32 A @ A.T of the centred "
+            "stack (device)", n,
+            ab(lambda: consensus.pairwise_sqdist(xs, z),
+               lambda: (lambda A: A @ A.T)(torch.stack(xs) - z)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table here")
     ap.add_argument("--section", default="all",
                     choices=["all", "penalty", "aggregate", "bb",
-                             "robust"])
+                             "robust", "krum"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_penalty needs a GPU")
@@ -353,6 +396,8 @@ def main():
         bb_section(dev, row)
     if args.section in ("all", "robust"):
         robust_section(dev, row)
+    if args.section in ("all", "krum"):
+        krum_section(dev, row)
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
