@@ -1,7 +1,7 @@
-// Shared by the aggregation kernels (consensus.hip, robust.hip, krum.hip):
-// the client table, the aligned 16-byte and unit-wide accessors, the
-// workgroup sum and the attribute of kernels whose results are compared bit
-// for bit.
+// Shared by the aggregation kernels (consensus.hip, robust.hip, krum.hip,
+// geomed.hip): the client table, the aligned 16-byte and unit-wide
+// accessors, the workgroup sum and the attribute of kernels whose results
+// are compared bit for bit.
 #pragma once
 
 #include "fedkit_common.h"

@@ -62,6 +62,10 @@ std::vector<at::Tensor> fedkit_krum_round(std::vector<at::Tensor> xs,
                                           const at::Tensor& z,
                                           const at::Tensor& center, double rho,
                                           int64_t mode, int64_t f, int64_t m);
+std::vector<at::Tensor> fedkit_geomed_round(std::vector<at::Tensor> xs,
+                                            const at::Tensor& z, double rho,
+                                            int64_t mode, int64_t iters,
+                                            double nu);
 
 std::vector<at::Tensor> fedkit_cross_entropy_fwd(const at::Tensor& logits,
                                                  const at::Tensor& labels);
@@ -225,6 +229,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "scores) with res as aggregate_round's",
         py::arg("xs"), py::arg("z"), py::arg("center"), py::arg("rho"),
         py::arg("mode"), py::arg("f"), py::arg("m"));
+  m.def("geomed_round", &fedkit_geomed_round,
+        "geometric-median (RFA) round over K <= 32 clients (mode 0 fedavg, 1 "
+        "fedprox): `iters` smoothed Weiszfeld steps on the MFMA Gram matrix "
+        "of xs[k] - z, then znew = z + sum c_k (xs[k] - z); returns (znew, "
+        "res, c fp32 [K], keep int32 [K], d fp32 [K]) with res as "
+        "aggregate_round's",
+        py::arg("xs"), py::arg("z"), py::arg("rho"), py::arg("mode"),
+        py::arg("iters"), py::arg("nu"));
   m.def("cross_entropy_fwd", &fedkit_cross_entropy_fwd,
         "fused log-softmax + NLL (mean): returns (loss, lse)");
   m.def("cross_entropy_bwd", &fedkit_cross_entropy_bwd, "CE backward");

@@ -64,25 +64,36 @@ class Strategy:
     # floor(trim_frac * K) values at each end of every coordinate's K client
     # values, "median" all but the middle one or two; "krum" keeps the one
     # client closest to its K - f - 2 nearest neighbours and "multi_krum"
-    # averages the K - f best such, f = floor(trim_frac * K); None is the
-    # mean.
+    # averages the K - f best such, f = floor(trim_frac * K); "geomed" is the
+    # geometric median, geomed_iters smoothed Weiszfeld steps that re-weight
+    # the clients and drop none; None is the mean.
     robust: Optional[str] = None
     trim_frac: float = 0.1
+    geomed_iters: int = 16
 
-    def _set_robust(self, robust: Optional[str], trim_frac: float):
+    def _set_robust(self, robust: Optional[str], trim_frac: float,
+                    geomed_iters: int = 16):
         if robust is not None and robust not in consensus.ROBUST_RULES:
             raise ValueError(f"unknown robust rule {robust!r}; one of "
                              f"{consensus.ROBUST_RULES}")
         self.robust, self.trim_frac = robust, float(trim_frac)
+        self.geomed_iters = int(geomed_iters)
 
     def _robust_round(self, comm: Communicator, state: dict, pending,
                       rho: Optional[float], mode: str):
         """Every rank runs the same round over the K gathered vectors: one
         pass of consensus.robust_round (HIP on a GPU), or the torch sequence
         that defines it when fused_aggregate is off; same z either way.  The
-        Krum rules leave their selection in state["krum_selected"]."""
+        Krum rules leave their selection in state["krum_selected"], the
+        geometric median its weights in state["geomed_weights"]."""
         fused = (self.fused_aggregate
                  and comm.K <= consensus.MAX_FUSED_CLIENTS)
+        if self.robust == "geomed":
+            fn = (consensus.geomed_round if fused
+                  else consensus.geomed_round_torch)
+            znew, res, state["geomed_weights"] = fn(
+                pending(), state["z"], rho, mode, self.geomed_iters)
+            return znew, res
         if self.robust in consensus.KRUM_RULES:
             f, m = consensus.krum_params(self.robust, self.trim_frac, comm.K)
             if fused:
@@ -150,8 +161,9 @@ class FedAvg(Strategy):
     name = "fedavg"
     writeback_z = True
 
-    def __init__(self, robust: Optional[str] = None, trim_frac: float = 0.1):
-        self._set_robust(robust, trim_frac)
+    def __init__(self, robust: Optional[str] = None, trim_frac: float = 0.1,
+                 geomed_iters: int = 16):
+        self._set_robust(robust, trim_frac, geomed_iters)
 
     def aggregate_start(self, comm, state, x):
         if self.robust:
@@ -197,8 +209,9 @@ class FedProx(Strategy):
     uses_penalty = True
 
     def __init__(self, rho0: float = 1.0, warmup_rounds: int = 0,
-                 robust: Optional[str] = None, trim_frac: float = 0.1):
-        self._set_robust(robust, trim_frac)
+                 robust: Optional[str] = None, trim_frac: float = 0.1,
+                 geomed_iters: int = 16):
+        self._set_robust(robust, trim_frac, geomed_iters)
         self.rho0 = rho0
         # engine extension, default 0 = reference behavior (see
         # ConsensusADMM.warmup_rounds: z starts at 0 per block, so the

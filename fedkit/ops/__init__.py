@@ -23,6 +23,10 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
                                  Gram pass over the centred vectors, on-device
                                  scoring and selection, mean of the selected
                                  clients with residuals (FedAvg/FedProx)
+  geomed_round                   geometric-median (RFA) round over K clients:
+                                 the same Gram pass, smoothed Weiszfeld on the
+                                 K x K matrix on the device, one weighted pass
+                                 with residuals (FedAvg/FedProx)
 
 Dispatch policy (this is the "native code is THE path that runs" rule):
   * on a ROCm GPU the HIP kernels are used; if the extension is missing the

@@ -21,7 +21,9 @@ coordinate-wise trimmed mean or median over the K clients in one pass
 (csrc/robust.hip).  `krum_round` is the distance-based form (Krum /
 Multi-Krum): `pairwise_sqdist` from an MFMA Gram pass over the centred
 vectors, the selection on the device, and the mean of the selected clients
-(csrc/krum.hip).
+(csrc/krum.hip).  `geomed_round` is the geometric median (RFA): smoothed
+Weiszfeld re-weighting of the clients, iterated on the same Gram matrix on
+the device, and one weighted pass (csrc/geomed.hip).
 
 All vectors are fp32 in PHYSICAL (storage) element order, the order
 flat.pack / paramvec.flat_physical use.  Dispatch follows the package rule:
@@ -204,7 +206,7 @@ def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
 
 
 KRUM_RULES = ("krum", "multi_krum")
-ROBUST_RULES = ("trimmed_mean", "median") + KRUM_RULES
+ROBUST_RULES = ("trimmed_mean", "median") + KRUM_RULES + ("geomed",)
 
 
 def robust_trim(rule: str, trim_frac: float, K: int) -> int:
@@ -385,6 +387,104 @@ def krum_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
             int(f), int(m))
         return znew, res, sel.bool()
     return krum_round_torch(xs, z, rho, mode, f, m)
+
+
+def geomed_round_torch(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                       rho: Optional[float] = None, mode: str = "fedavg",
+                       iters: int = 16, nu: float = 1e-3):
+    """The torch sequence that defines `geomed_round` (the rule is stated
+    there), on the operands' device and in their dtype, directly on the
+    vectors; returns (znew, res, c).  It reads the kept set on the host."""
+    if mode == "admm":
+        raise ValueError("there is no robust ADMM round; use fedavg or fedprox")
+    assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+    if not 1 <= iters <= 1024 or not (nu > 0 and math.isfinite(nu)):
+        raise ValueError(f"geomed_round needs 1 <= iters <= 1024 and a finite "
+                         f"nu > 0, got iters = {iters}, nu = {nu}")
+    xs = list(xs)
+    sq = torch.stack([((x - z) ** 2).sum() for x in xs])
+    kept = sq.isfinite().nonzero().flatten().tolist()
+    Kp = len(kept)
+    mid = (Kp - 1) // 2
+    c = torch.zeros_like(sq)
+    floor = nu * sq[kept].sort().values[mid].sqrt() if Kp else 0.0
+    if Kp == 0:
+        pass
+    elif float(floor) == 0.0 or Kp <= 2:
+        c[kept] = 1.0 / Kp
+    else:
+        pair = {(i, j): ((xs[i] - xs[j]) ** 2).sum()
+                for i in kept for j in kept if i < j}
+        r = torch.stack([
+            torch.stack([pair[min(i, j), max(i, j)] for j in kept if j != i])
+            .sort().values[mid] for i in kept]).sqrt()
+        w = 1.0 / torch.maximum(floor, r)
+        ck = w / w.sum()
+        for _ in range(iters):
+            v = z.clone()
+            for j, k in enumerate(kept):
+                v += ck[j] * (xs[k] - z)
+            d = torch.stack([((xs[k] - v) ** 2).sum() for k in kept]).sqrt()
+            w = 1.0 / torch.maximum(floor, d)
+            ck = w / w.sum()
+        c[kept] = ck
+    znew = z.clone()
+    for k in kept:
+        znew += c[k] * (xs[k] - z)
+    res = [torch.norm(z - znew) ** 2]
+    if mode != "fedavg":
+        res += [torch.norm(rho * (x - znew)) ** 2 for x in xs]
+    return znew, torch.stack(res), c
+
+
+def geomed_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                 rho: Optional[float] = None, mode: str = "fedavg",
+                 iters: int = 16, nu: float = 1e-3):
+    """One geometric-median aggregation round (RFA: Pillutla, Kakade and
+    Harchaoui, 2022) over the K client vectors `xs`: the clients are
+    re-weighted by smoothed Weiszfeld steps, none is dropped, and up to half
+    of them may hold anything.  The rule:
+
+      1. keep[k] = sum((xs[k] - z)^2) is finite; a client that is not kept
+         has weight exactly 0 and is multiplied by nothing.  K' = number
+         kept; K' = 0 gives c = 0 and znew = z.
+      2. r_k = the median distance from kept client k to the other kept
+         clients, s = the median of the kept ||x_k - z||, both medians the
+         value at 0-based index (K' - 1) // 2 of the ascending values.
+      3. floor = nu * s.  floor == 0 or K' <= 2: c = 1 / K' on the kept
+         clients.  Otherwise c_k ~ 1 / max(floor, r_k), normalised to sum 1,
+         then exactly `iters` times d_k = max(floor, ||x_k - v||) with
+         v = z + sum_j c_j (x_j - z), and c_k ~ 1 / d_k, normalised.
+      4. znew = z.clone(); znew += c[k] * (xs[k] - z) for kept k ascending.
+
+    The median-distance start and the median-scaled floor keep a colluding
+    far-away minority from capturing the first iterate.
+
+    Returns (znew, res, c): znew and res as `robust_round` (res[1 + k] for
+    all K clients in fedprox mode, NaN for a NaN client), c the fp32 [K]
+    weights on z's device, formed without a host sync.  Modes are fedavg and
+    fedprox; 1 <= iters <= 1024, nu finite and > 0.  On the GPU
+    (csrc/geomed.hip, K <= 32) Weiszfeld runs on the MFMA Gram matrix of
+    xs[k] - z, two passes over the operands whatever `iters` is, and znew is
+    bitwise the sequence of step 4 over the kernel's own c and keep; c
+    agrees with `geomed_round_torch`, the CPU path, to the Gram matrix's
+    rounding.  That error scales with ||xs[k] - z||^2, so z should be close
+    to the clients (the old consensus is); at a block's round 0 the
+    consensus is 0 and the conditioning is that of the raw vectors.
+    Distances below about 7e-4 of the centred norm are not resolved, which
+    is what the default nu covers.
+    """
+    xs = list(xs)
+    if mode != "fedavg" and mode != "admm":
+        assert rho is not None, f"{mode} needs rho"
+    if _use_native(z):
+        assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+        from . import require_ext
+        znew, res, c, _, _ = require_ext().geomed_round(
+            xs, z, 0.0 if rho is None else float(rho),
+            AGGREGATE_MODES.index(mode), int(iters), float(nu))
+        return znew, res, c
+    return geomed_round_torch(xs, z, rho, mode, iters, nu)
 
 
 def bb_stats(y: torch.Tensor, yhat0: torch.Tensor, x: torch.Tensor,

@@ -112,12 +112,14 @@ class FedConfig:
                                        # torch sequence; same z and y bits)
     robust_agg: str = "none"           # none | trimmed_mean | median (the
                                        # coordinate-wise rules) | krum |
-                                       # multi_krum (distance-based) of a
+                                       # multi_krum (distance-based) | geomed
+                                       # (geometric median, RFA) of a
                                        # FedAvg / FedProx round (none = mean)
     trim_frac: float = 0.1             # trimmed_mean drops floor(trim_frac*K)
                                        # client values at each end; the Krum
                                        # rules take f = floor(trim_frac*K)
                                        # as the number of bad clients
+    geomed_iters: int = 16             # geomed: smoothed Weiszfeld steps
 
     def model_name(self) -> str:
         if self.model:
@@ -131,7 +133,8 @@ class FedConfig:
 
     def _make_strategy(self) -> Strategy:
         robust = dict(robust=None if self.robust_agg == "none"
-                      else self.robust_agg, trim_frac=self.trim_frac)
+                      else self.robust_agg, trim_frac=self.trim_frac,
+                      geomed_iters=self.geomed_iters)
         if self.strategy == "none":
             return NoConsensus()
         if self.strategy == "fedavg":

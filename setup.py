@@ -21,6 +21,7 @@ SOURCES = [
     "csrc/consensus.hip",
     "csrc/robust.hip",
     "csrc/krum.hip",
+    "csrc/geomed.hip",
     "csrc/loss.hip",
     "csrc/losses_extra.hip",
     "csrc/linear.hip",

@@ -46,6 +46,14 @@ further rows against robust_round (trim = f) and the plain mean of
 aggregate_round at the same K and N.  Device time; the torch sequence is
 timed by the wall clock, since it reads the selection on the host.
 
+Section `geomed`: one geometric-median round (iters = 16) at K = 10 and
+K = 32, the two N of `aggregate`, fedavg / fedprox: consensus.geomed_round
+(csrc/geomed.hip) against geomed_round_torch on the GPU (wall: it reads the
+kept set on the host), and device-time rows against krum_round (Multi-Krum,
+f = K // 5) and the plain mean of aggregate_round.  Two further rows per K
+time the same round with iters = 1 and iters = 1024: the differences are
+the solver's iterations alone.
+
 Method: warm-up, then SAMPLES samples per path taken alternately (fused,
 torch, fused, ...), each sample ITERS back-to-back calls between two device
 events; the reported figure is the median sample in microseconds per call.
@@ -305,12 +313,54 @@ def krum_section(dev, row):
                lambda: (lambda A: A @ A.T)(torch.stack(xs) - z)))
 
 
+def geomed_section(dev, row):
+    for name, n in AGG_SIZES.items():
+        for K in (10, 32):
+            g = torch.Generator().manual_seed(6)
+            z = (torch.randn(n, generator=g) * 0.05).to(dev)
+            xs = [z + (torch.randn(n, generator=g) * 0.01).to(dev)
+                  for _ in range(K)]
+            f = K // 5
+            for mode in ("fedavg", "fedprox"):
+                def fused(iters=16):
+                    return consensus.geomed_round(xs, z, RHO, mode, iters)
+
+                def sequence():
+                    return consensus.geomed_round_torch(xs, z, RHO, mode)
+
+                (za, _, ca), (zb, _, cb) = fused(), sequence()
+                print(f"{name} geomed {mode} K={K}: max |c - c_torch| / max c "
+                      f"{float((ca - cb).abs().max() / cb.max()):.3g}, "
+                      f"max |znew - znew_torch| "
+                      f"{float((za - zb).abs().max()):.3g}", flush=True)
+                row(f"{name}: geomed {mode} K={K} iters=16 (wall)", n,
+                    ab(fused, sequence, sampler=sample_wall_us))
+                row(f"{name}: geomed {mode} vs multi_krum f={f} K={K} "
+                    "(device; columns: geomed, krum, krum/geomed)", n,
+                    ab(fused,
+                       lambda: consensus.krum_round(xs, z, RHO, mode, f)))
+                row(f"{name}: geomed {mode} vs plain mean K={K} "
+                    "(device; columns: geomed, mean, mean/geomed)", n,
+                    ab(fused, lambda: consensus.aggregate_round(
+                        xs, z, rho=RHO, mode=mode)))
+            # the solver: 15 and 1008 further iterations of the same round
+            def fedavg(iters=16):
+                return consensus.geomed_round(xs, z, RHO, "fedavg", iters)
+
+            row(f"{name}: geomed fedavg K={K} iters=16 vs iters=1 "
+                "(device; columns: 16, 1, 1/16)", n,
+                ab(fedavg, lambda: fedavg(1)))
+            row(f"{name}: geomed fedavg K={K} iters=16 vs iters=1024 "
+                "(device; columns: 16, 1024, 1024/16)", n,
+                ab(fedavg, lambda: fedavg(1024)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table here")
     ap.add_argument("--section", default="all",
                     choices=["all", "penalty", "aggregate", "bb",
-                             "robust", "krum"])
+                             "robust", "krum", "geomed"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_penalty needs a GPU")
@@ -398,6 +448,8 @@ def main():
         robust_section(dev, row)
     if args.section in ("all", "krum"):
         krum_section(dev, row)
+    if args.section in ("all", "geomed"):
+        geomed_section(dev, row)
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
