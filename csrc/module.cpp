@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "conv_plan.h"
+#include "linear_plan.h"
 
 at::Tensor fedkit_elu_fwd(const at::Tensor& x);
 std::vector<at::Tensor> fedkit_max_pool2d_fwd(const at::Tensor& x, long k);
@@ -129,6 +130,13 @@ at::Tensor fedkit_linear_bwd_data(const at::Tensor& gy, const at::Tensor& w);
 std::vector<at::Tensor> fedkit_linear_bwd_weight(const at::Tensor& gy,
                                                  const at::Tensor& x,
                                                  bool want_bias);
+at::Tensor fedkit_linear_mfma_fwd(const at::Tensor& x, const at::Tensor& w,
+                                  const c10::optional<at::Tensor>& bias);
+at::Tensor fedkit_linear_mfma_bwd_data(const at::Tensor& gy,
+                                       const at::Tensor& w);
+std::vector<at::Tensor> fedkit_linear_mfma_bwd_weight(const at::Tensor& gy,
+                                                      const at::Tensor& x,
+                                                      bool want_bias);
 
 at::Tensor fedkit_conv2d_dilated_bank(const at::Tensor& x,
                                       const at::Tensor& w2d,
@@ -327,6 +335,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_bwd_weight", &fedkit_linear_bwd_weight,
         "linear bwd-weight (+bias): fp32 grads",
         py::arg("gy"), py::arg("x"), py::arg("want_bias") = true);
+  m.def("linear_mfma_fwd", &fedkit_linear_mfma_fwd,
+        "bf16 MFMA linear fwd (x [M,K], w [N,K], fp32 bias) -> bf16 [M,N]; "
+        "K and N multiples of 8",
+        py::arg("x"), py::arg("w"), py::arg("bias") = c10::nullopt);
+  m.def("linear_mfma_bwd_data", &fedkit_linear_mfma_bwd_data,
+        "bf16 MFMA linear bwd-data (gy [M,N], w [N,K]) -> bf16 [M,K]");
+  m.def("linear_mfma_bwd_weight", &fedkit_linear_mfma_bwd_weight,
+        "bf16 MFMA linear bwd-weight (+bias): fp32 grads",
+        py::arg("gy"), py::arg("x"), py::arg("want_bias") = true);
+  m.def("linear_mfma_plan",
+        [](long M, long N, long K) {
+          auto f = fedkit_plan::plan_linear(M, N, K, true);
+          auto d = fedkit_plan::plan_linear(M, K, N, true);
+          auto w = fedkit_plan::plan_linear(N, K, M, false);
+          return py::make_tuple(
+              py::make_tuple(f.tiles_i, f.tiles_j, f.splits, f.kt_per_split),
+              py::make_tuple(d.tiles_i, d.tiles_j, d.splits, d.kt_per_split),
+              py::make_tuple(w.tiles_i, w.tiles_j, w.splits, w.kt_per_split));
+        },
+        "MFMA linear launch plans of (fwd, bwd-data, bwd-weight), each "
+        "(tiles_i, tiles_j, splits, kt_per_split)",
+        py::arg("M"), py::arg("N"), py::arg("K"));
   m.def("conv2d_dilated_bank", &fedkit_conv2d_dilated_bank,
         "fused multi-dilation conv bank: n taps, one input, one launch "
         "(block-diagonal combined weight)");

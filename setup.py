@@ -25,6 +25,7 @@ SOURCES = [
     "csrc/loss.hip",
     "csrc/losses_extra.hip",
     "csrc/linear.hip",
+    "csrc/linear_mfma.hip",
     "csrc/adam.hip",
     "csrc/batchnorm.hip",
     "csrc/conv2d_mfma.hip",
