@@ -1,6 +1,6 @@
-// The MFMA Gram pass shared by krum.hip and geomed.hip: G = A A^T of the
-// K x N matrix of centred client vectors a_k = x_k - c, K <= 32, as per
-// workgroup partials, and their sum in double.  The design notes (staging,
+// The MFMA Gram pass shared by krum.hip, geomed.hip and cclip.hip: G = A A^T
+// of the K x N matrix of centred client vectors a_k = x_k - c, K <= 32, as
+// per workgroup partials, and their sum in double.  The design notes (staging,
 // double buffering, MFMA operand layout, LDS banks) are at the head of
 // krum.hip.
 #pragma once
@@ -137,7 +137,7 @@ __device__ __forceinline__ double gram_entry(const float* __restrict__ part,
 }
 
 // The passes that follow the Gram pass (select_mean_kernel of krum.hip,
-// weighted_delta_kernel of geomed.hip) hold up to bucket_of(rows) client
+// weighted_delta_kernel of weighted_delta.h) hold up to bucket_of(rows) client
 // rows per thread.  Unit width of a bucket (tables at fedkit_krum_round and
 // fedkit_geomed_round): 16-byte loads except where fedprox holds more than
 // 16 clients' values.

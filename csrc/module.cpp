@@ -67,6 +67,11 @@ std::vector<at::Tensor> fedkit_geomed_round(std::vector<at::Tensor> xs,
                                             const at::Tensor& z, double rho,
                                             int64_t mode, int64_t iters,
                                             double nu);
+std::vector<at::Tensor> fedkit_cclip_round(std::vector<at::Tensor> xs,
+                                           const at::Tensor& z, double rho,
+                                           int64_t mode, int64_t iters,
+                                           double tau, int64_t bucket,
+                                           const at::Tensor& perm);
 
 std::vector<at::Tensor> fedkit_cross_entropy_fwd(const at::Tensor& logits,
                                                  const at::Tensor& labels);
@@ -245,6 +250,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "aggregate_round's",
         py::arg("xs"), py::arg("z"), py::arg("rho"), py::arg("mode"),
         py::arg("iters"), py::arg("nu"));
+  m.def("cclip_round", &fedkit_cclip_round,
+        "centred-clipping round with bucketing over K <= 32 clients (mode 0 "
+        "fedavg, 1 fedprox): means of groups of `bucket` clients in the order "
+        "of `perm` (int32 [K] on the device), `iters` clip steps of radius "
+        "`tau` (0: the median bucket norm) on the MFMA Gram matrix of "
+        "xs[k] - z, then znew = z + sum w_k (xs[k] - z); returns (znew, res, "
+        "w fp32 [K], keep int32 [K], d fp32 [K], tau_used fp32 [1]) with res "
+        "as aggregate_round's",
+        py::arg("xs"), py::arg("z"), py::arg("rho"), py::arg("mode"),
+        py::arg("iters"), py::arg("tau"), py::arg("bucket"), py::arg("perm"));
   m.def("cross_entropy_fwd", &fedkit_cross_entropy_fwd,
         "fused log-softmax + NLL (mean): returns (loss, lse)");
   m.def("cross_entropy_bwd", &fedkit_cross_entropy_bwd, "CE backward");

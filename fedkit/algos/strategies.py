@@ -66,28 +66,59 @@ class Strategy:
     # client closest to its K - f - 2 nearest neighbours and "multi_krum"
     # averages the K - f best such, f = floor(trim_frac * K); "geomed" is the
     # geometric median, geomed_iters smoothed Weiszfeld steps that re-weight
-    # the clients and drop none; None is the mean.
+    # the clients and drop none; "cclip" is centred clipping: cclip_iters
+    # clip steps of radius cclip_tau (0 = the median norm) around the old z,
+    # over the means of random groups of agg_bucket clients (1 = the clients
+    # themselves); None is the mean.
     robust: Optional[str] = None
     trim_frac: float = 0.1
     geomed_iters: int = 16
+    cclip_iters: int = 3
+    cclip_tau: float = 0.0
+    agg_bucket: int = 1
+    agg_seed: int = 0       # the job seed: the bucket permutations' stream
 
     def _set_robust(self, robust: Optional[str], trim_frac: float,
-                    geomed_iters: int = 16):
+                    geomed_iters: int = 16, cclip_iters: int = 3,
+                    cclip_tau: float = 0.0, agg_bucket: int = 1,
+                    agg_seed: int = 0):
         if robust is not None and robust not in consensus.ROBUST_RULES:
             raise ValueError(f"unknown robust rule {robust!r}; one of "
                              f"{consensus.ROBUST_RULES}")
+        if agg_bucket != 1 and robust != "cclip":
+            raise ValueError("agg_bucket needs robust rule 'cclip': the other "
+                             "rules have no bucketing")
         self.robust, self.trim_frac = robust, float(trim_frac)
         self.geomed_iters = int(geomed_iters)
+        self.cclip_iters, self.cclip_tau = int(cclip_iters), float(cclip_tau)
+        self.agg_bucket, self.agg_seed = int(agg_bucket), int(agg_seed)
+
+    def _bucket_perm(self, K: int, round_idx: int):
+        """The round's client order for bucketing, drawn on the CPU from the
+        job seed and the round index: the same on every rank."""
+        if self.agg_bucket == 1:
+            return None
+        g = torch.Generator().manual_seed(self.agg_seed * 1000003 + round_idx)
+        return torch.randperm(K, generator=g)
 
     def _robust_round(self, comm: Communicator, state: dict, pending,
-                      rho: Optional[float], mode: str):
+                      rho: Optional[float], mode: str, round_idx: int = 0):
         """Every rank runs the same round over the K gathered vectors: one
         pass of consensus.robust_round (HIP on a GPU), or the torch sequence
         that defines it when fused_aggregate is off; same z either way.  The
         Krum rules leave their selection in state["krum_selected"], the
-        geometric median its weights in state["geomed_weights"]."""
+        geometric median its weights in state["geomed_weights"], centred
+        clipping its weights in state["cclip_weights"]."""
         fused = (self.fused_aggregate
                  and comm.K <= consensus.MAX_FUSED_CLIENTS)
+        if self.robust == "cclip":
+            fn = (consensus.cclip_round if fused
+                  else consensus.cclip_round_torch)
+            znew, res, state["cclip_weights"] = fn(
+                pending(), state["z"], rho, mode, self.cclip_iters,
+                self.cclip_tau, self.agg_bucket,
+                self._bucket_perm(comm.K, round_idx))
+            return znew, res
         if self.robust == "geomed":
             fn = (consensus.geomed_round if fused
                   else consensus.geomed_round_torch)
@@ -162,8 +193,8 @@ class FedAvg(Strategy):
     writeback_z = True
 
     def __init__(self, robust: Optional[str] = None, trim_frac: float = 0.1,
-                 geomed_iters: int = 16):
-        self._set_robust(robust, trim_frac, geomed_iters)
+                 geomed_iters: int = 16, **cclip):
+        self._set_robust(robust, trim_frac, geomed_iters, **cclip)
 
     def aggregate_start(self, comm, state, x):
         if self.robust:
@@ -177,7 +208,7 @@ class FedAvg(Strategy):
         z, N = state["z"], state["N"]
         if self.robust:
             znew, res = self._robust_round(comm, state, pending, None,
-                                           "fedavg")
+                                           "fedavg", round_idx)
             state["z"] = znew
             return {"dual": torch.sqrt(res[0]) / N}
         if pending is None:
@@ -210,8 +241,8 @@ class FedProx(Strategy):
 
     def __init__(self, rho0: float = 1.0, warmup_rounds: int = 0,
                  robust: Optional[str] = None, trim_frac: float = 0.1,
-                 geomed_iters: int = 16):
-        self._set_robust(robust, trim_frac, geomed_iters)
+                 geomed_iters: int = 16, **cclip):
+        self._set_robust(robust, trim_frac, geomed_iters, **cclip)
         self.rho0 = rho0
         # engine extension, default 0 = reference behavior (see
         # ConsensusADMM.warmup_rounds: z starts at 0 per block, so the
@@ -268,7 +299,7 @@ class FedProx(Strategy):
         if self.robust:
             # all K residuals are formed on every rank: nothing to gather
             znew, res = self._robust_round(comm, state, pending, rho,
-                                           "fedprox")
+                                           "fedprox", round_idx)
             sq = res.tolist()
             state["z"] = znew
             state["round"] = round_idx + 1

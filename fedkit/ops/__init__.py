@@ -27,6 +27,10 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
                                  the same Gram pass, smoothed Weiszfeld on the
                                  K x K matrix on the device, one weighted pass
                                  with residuals (FedAvg/FedProx)
+  cclip_round                    centred-clipping round with bucketing over K
+                                 clients: the same Gram pass, the bucket
+                                 contraction and the clip iterations on the
+                                 device, the same weighted pass (FedAvg/FedProx)
 
 Dispatch policy (this is the "native code is THE path that runs" rule):
   * on a ROCm GPU the HIP kernels are used; if the extension is missing the

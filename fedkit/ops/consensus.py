@@ -23,7 +23,10 @@ Multi-Krum): `pairwise_sqdist` from an MFMA Gram pass over the centred
 vectors, the selection on the device, and the mean of the selected clients
 (csrc/krum.hip).  `geomed_round` is the geometric median (RFA): smoothed
 Weiszfeld re-weighting of the clients, iterated on the same Gram matrix on
-the device, and one weighted pass (csrc/geomed.hip).
+the device, and one weighted pass (csrc/geomed.hip).  `cclip_round` is
+centred clipping with bucketing: the clients are averaged in random groups,
+the group means are clipped towards the old consensus, again iterated on the
+Gram matrix on the device, and the same weighted pass (csrc/cclip.hip).
 
 All vectors are fp32 in PHYSICAL (storage) element order, the order
 flat.pack / paramvec.flat_physical use.  Dispatch follows the package rule:
@@ -206,7 +209,7 @@ def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
 
 
 KRUM_RULES = ("krum", "multi_krum")
-ROBUST_RULES = ("trimmed_mean", "median") + KRUM_RULES + ("geomed",)
+ROBUST_RULES = ("trimmed_mean", "median") + KRUM_RULES + ("geomed", "cclip")
 
 
 def robust_trim(rule: str, trim_frac: float, K: int) -> int:
@@ -485,6 +488,149 @@ def geomed_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
             AGGREGATE_MODES.index(mode), int(iters), float(nu))
         return znew, res, c
     return geomed_round_torch(xs, z, rho, mode, iters, nu)
+
+
+def _cclip_perm(perm, K: int):
+    """`perm` as a list of K ints, checked on the host: a permutation of
+    0..K-1 (None: the identity)."""
+    if perm is None:
+        return list(range(K))
+    if isinstance(perm, torch.Tensor):
+        if perm.device.type != "cpu":
+            raise ValueError("cclip_round takes perm as a sequence or a CPU "
+                             "tensor: its contents are checked on the host")
+        perm = perm.tolist()
+    perm = [int(p) for p in perm]
+    if sorted(perm) != list(range(K)):
+        raise ValueError(f"perm must be a permutation of 0..{K - 1}, got "
+                         f"{perm}")
+    return perm
+
+
+def _check_cclip(K: int, mode: str, iters: int, tau: float, bucket: int):
+    if mode == "admm":
+        raise ValueError("there is no robust ADMM round; use fedavg or fedprox")
+    assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+    if (not 1 <= iters <= 1024 or not (tau >= 0 and math.isfinite(tau))
+            or not 1 <= bucket <= K):
+        raise ValueError(f"cclip_round needs 1 <= iters <= 1024, a finite "
+                         f"tau >= 0 and 1 <= bucket <= K, got iters = {iters}, "
+                         f"tau = {tau}, bucket = {bucket}, K = {K}")
+
+
+def cclip_solve_torch(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                      iters: int = 3, tau: float = 0.0, bucket: int = 1,
+                      perm=None):
+    """Steps 1 to 5 of `cclip_round` directly on the vectors: returns (w,
+    kept, s, tau_used) with w the [K] client weights, kept the ascending
+    list of kept clients, s the [B] clip factors of the last iteration and
+    tau_used the radius.  It reads the kept set on the host."""
+    xs = list(xs)
+    perm = _cclip_perm(perm, len(xs))
+    sq = torch.stack([((x - z) ** 2).sum() for x in xs])
+    keep = sq.isfinite().tolist()
+    order = [k for k in perm if keep[k]]
+    groups = [order[i:i + bucket] for i in range(0, len(order), bucket)]
+    B = len(groups)
+    w = torch.zeros_like(sq)
+    if B == 0:
+        return w, [], sq[:0], sq.new_zeros(())
+    us = []
+    for g in groups:
+        u = torch.zeros_like(z)
+        for k in g:
+            u += xs[k] - z
+        us.append(u / len(g))
+    t = (sq.new_tensor(tau) if tau > 0 else
+         torch.stack([u.norm() for u in us]).sort().values[(B - 1) // 2])
+    c = sq.new_zeros(B)
+    for _ in range(iters):
+        v = torch.zeros_like(z)
+        for b in range(B):
+            v += c[b] * us[b]
+        dist = torch.stack([(u - v).norm() for u in us])
+        s = torch.where(dist > t, t / dist, torch.ones_like(dist))
+        c = c * (1 - s.sum() / B) + s / B
+    for b, g in enumerate(groups):
+        w[g] = c[b] / len(g)
+    return w, sorted(order), s, t
+
+
+def cclip_round_torch(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                      rho: Optional[float] = None, mode: str = "fedavg",
+                      iters: int = 3, tau: float = 0.0, bucket: int = 1,
+                      perm=None):
+    """The torch sequence that defines `cclip_round` (the rule is stated
+    there), on the operands' device and in their dtype, directly on the
+    vectors; returns (znew, res, w).  It reads the kept set on the host."""
+    xs = list(xs)
+    _check_cclip(len(xs), mode, iters, tau, bucket)
+    w, kept, _, _ = cclip_solve_torch(xs, z, iters, tau, bucket, perm)
+    znew = z.clone()
+    for k in kept:
+        znew += w[k] * (xs[k] - z)
+    res = [torch.norm(z - znew) ** 2]
+    if mode != "fedavg":
+        res += [torch.norm(rho * (x - znew)) ** 2 for x in xs]
+    return znew, torch.stack(res), w
+
+
+def cclip_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                rho: Optional[float] = None, mode: str = "fedavg",
+                iters: int = 3, tau: float = 0.0, bucket: int = 1, perm=None):
+    """One centred-clipping aggregation round (Karimireddy, He and Jaggi,
+    2021) with bucketing (the same authors, 2022) over the K client vectors
+    `xs`: no client is dropped, there is no breakdown point at a fixed
+    number of bad clients, and the clip radius bounds how far any set of
+    clients moves the consensus: ||znew - z|| <= iters * tau.  The rule:
+
+      1. keep[k] = sum((xs[k] - z)^2) is finite, as in `geomed_round`.
+         K' = number kept; K' = 0 gives w = 0 and znew = z.
+      2. Buckets: walk perm[0..K-1] (a permutation of 0..K-1, None = the
+         identity), skip the clients that are not kept and cut the rest
+         into consecutive groups of `bucket` = s; the last may be smaller,
+         B = ceil(K' / s).  u_b = the mean of xs[k] - z over bucket b.
+      3. The radius is `tau` if tau > 0, else the median of the ||u_b||:
+         the value at 0-based index (B - 1) // 2 of the ascending values.
+      4. c = 0 in R^B; exactly `iters` times dist_b = ||u_b - sum_j c_j u_j||,
+         s_b = tau / dist_b if dist_b > tau else 1, S = sum_b s_b and
+         c_b <- c_b (1 - S / B) + s_b / B, which is
+         v <- v + (1 / B) sum_b s_b (u_b - v) written in coefficients.
+      5. w_k = c_b(k) / |bucket b(k)| for kept k, 0 otherwise.  The weights
+         need not sum to 1.
+      6. znew = z.clone(); znew += w[k] * (xs[k] - z) for kept k ascending.
+
+    Bucketing with a fresh random `perm` per round is what makes the rule
+    (and any robust rule) usable on non-IID shards: the bucket means are
+    closer to each other than the clients are.
+
+    Returns (znew, res, w): znew and res as `robust_round` (res[1 + k] for
+    all K clients in fedprox mode, NaN for a NaN client), w the fp32 [K]
+    weights on z's device, formed without a host sync.  Modes are fedavg and
+    fedprox; 1 <= iters <= 1024, tau finite and >= 0, 1 <= bucket <= K.
+    `perm` is a sequence or a CPU tensor: its contents are checked on the
+    host.  On the GPU (csrc/cclip.hip, K <= 32) the buckets are a
+    contraction of the MFMA Gram matrix of xs[k] - z and the iteration runs
+    on that B x B matrix: two passes over the operands whatever `iters` and
+    `bucket` are, and znew is bitwise the sequence of step 6 over the
+    kernel's own w and keep; w agrees with `cclip_round_torch`, the CPU
+    path, to the Gram matrix's rounding.  A distance is inaccurate only
+    where a bucket is close to the iterate, and there its clip factor is
+    exactly 1.
+    """
+    xs = list(xs)
+    if mode != "fedavg" and mode != "admm":
+        assert rho is not None, f"{mode} needs rho"
+    if _use_native(z):
+        assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+        from . import require_ext
+        perm = torch.tensor(_cclip_perm(perm, len(xs)), dtype=torch.int32)
+        znew, res, w, _, _, _ = require_ext().cclip_round(
+            xs, z, 0.0 if rho is None else float(rho),
+            AGGREGATE_MODES.index(mode), int(iters), float(tau), int(bucket),
+            perm.to(z.device))
+        return znew, res, w
+    return cclip_round_torch(xs, z, rho, mode, iters, tau, bucket, perm)
 
 
 def bb_stats(y: torch.Tensor, yhat0: torch.Tensor, x: torch.Tensor,

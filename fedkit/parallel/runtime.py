@@ -113,13 +113,21 @@ class FedConfig:
     robust_agg: str = "none"           # none | trimmed_mean | median (the
                                        # coordinate-wise rules) | krum |
                                        # multi_krum (distance-based) | geomed
-                                       # (geometric median, RFA) of a
-                                       # FedAvg / FedProx round (none = mean)
+                                       # (geometric median, RFA) | cclip
+                                       # (centred clipping) of a FedAvg /
+                                       # FedProx round (none = mean)
     trim_frac: float = 0.1             # trimmed_mean drops floor(trim_frac*K)
                                        # client values at each end; the Krum
                                        # rules take f = floor(trim_frac*K)
                                        # as the number of bad clients
     geomed_iters: int = 16             # geomed: smoothed Weiszfeld steps
+    cclip_iters: int = 3               # cclip: clip steps around the old z
+    cclip_tau: float = 0.0             # cclip: clip radius; 0 = the median
+                                       # norm of the (bucketed) updates
+    agg_bucket: int = 1                # cclip: average random groups of this
+                                       # many clients before the rule (the
+                                       # permutation of a round comes from
+                                       # seed and the round index); 1 = off
 
     def model_name(self) -> str:
         if self.model:
@@ -134,7 +142,9 @@ class FedConfig:
     def _make_strategy(self) -> Strategy:
         robust = dict(robust=None if self.robust_agg == "none"
                       else self.robust_agg, trim_frac=self.trim_frac,
-                      geomed_iters=self.geomed_iters)
+                      geomed_iters=self.geomed_iters,
+                      cclip_iters=self.cclip_iters, cclip_tau=self.cclip_tau,
+                      agg_bucket=self.agg_bucket, agg_seed=self.seed)
         if self.strategy == "none":
             return NoConsensus()
         if self.strategy == "fedavg":

@@ -22,6 +22,7 @@ SOURCES = [
     "csrc/robust.hip",
     "csrc/krum.hip",
     "csrc/geomed.hip",
+    "csrc/cclip.hip",
     "csrc/loss.hip",
     "csrc/losses_extra.hip",
     "csrc/linear.hip",

@@ -54,6 +54,13 @@ f = K // 5) and the plain mean of aggregate_round.  Two further rows per K
 time the same round with iters = 1 and iters = 1024: the differences are
 the solver's iterations alone.
 
+Section `cclip`: one centred-clipping round (iters = 3) at the K and N of
+`geomed`, fedavg / fedprox, bucket s = 1 and s = 2 (a seeded permutation):
+consensus.cclip_round (csrc/cclip.hip) against cclip_round_torch on the GPU
+(wall: it reads the kept set on the host), and a device-time row against
+geomed_round at the same K, N and iters.  One further row per K times
+iters = 3 against iters = 1024.
+
 Method: warm-up, then SAMPLES samples per path taken alternately (fused,
 torch, fused, ...), each sample ITERS back-to-back calls between two device
 events; the reported figure is the median sample in microseconds per call.
@@ -355,12 +362,52 @@ def geomed_section(dev, row):
                 ab(fedavg, lambda: fedavg(1024)))
 
 
+def cclip_section(dev, row):
+    iters = 3
+    for name, n in AGG_SIZES.items():
+        for K in (10, 32):
+            g = torch.Generator().manual_seed(7)
+            z = (torch.randn(n, generator=g) * 0.05).to(dev)
+            xs = [z + (torch.randn(n, generator=g) * 0.01).to(dev)
+                  for _ in range(K)]
+            perm = torch.randperm(K, generator=g)
+            for mode in ("fedavg", "fedprox"):
+                for s in (1, 2):
+                    def fused(iters=iters, s=s):
+                        return consensus.cclip_round(xs, z, RHO, mode, iters,
+                                                     0.0, s, perm)
+
+                    def sequence(s=s):
+                        return consensus.cclip_round_torch(
+                            xs, z, RHO, mode, iters, 0.0, s, perm)
+
+                    (za, _, wa), (zb, _, wb) = fused(), sequence()
+                    print(f"{name} cclip {mode} K={K} s={s}: max |w - w_torch|"
+                          f" / max w {float((wa - wb).abs().max() / wb.max()):.3g}"
+                          f", max |znew - znew_torch| "
+                          f"{float((za - zb).abs().max()):.3g}", flush=True)
+                    row(f"{name}: cclip {mode} K={K} s={s} iters={iters} "
+                        "(wall)", n, ab(fused, sequence,
+                                        sampler=sample_wall_us))
+                    row(f"{name}: cclip {mode} s={s} vs geomed K={K} "
+                        f"iters={iters} (device; columns: cclip, geomed, "
+                        "geomed/cclip)", n,
+                        ab(fused, lambda: consensus.geomed_round(
+                            xs, z, RHO, mode, iters)))
+            row(f"{name}: cclip fedavg K={K} s=2 iters={iters} vs iters=1024 "
+                f"(device; columns: {iters}, 1024, 1024/{iters})", n,
+                ab(lambda: consensus.cclip_round(xs, z, RHO, "fedavg", iters,
+                                                 0.0, 2, perm),
+                   lambda: consensus.cclip_round(xs, z, RHO, "fedavg", 1024,
+                                                 0.0, 2, perm)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table here")
     ap.add_argument("--section", default="all",
                     choices=["all", "penalty", "aggregate", "bb",
-                             "robust", "krum", "geomed"])
+                             "robust", "krum", "geomed", "cclip"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_penalty needs a GPU")
@@ -450,6 +497,8 @@ def main():
         krum_section(dev, row)
     if args.section in ("all", "geomed"):
         geomed_section(dev, row)
+    if args.section in ("all", "cclip"):
+        cclip_section(dev, row)
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
