@@ -1,5 +1,5 @@
 // Shared by the aggregation kernels (consensus.hip, robust.hip, krum.hip,
-// geomed.hip, cclip.hip): the client table, the aligned 16-byte and unit-wide
+// geomed.hip, cclip.hip, bulyan.hip): the client table, the aligned 16-byte and unit-wide
 // accessors, the workgroup sum and the attribute of kernels whose results
 // are compared bit for bit.
 #pragma once

@@ -72,6 +72,11 @@ std::vector<at::Tensor> fedkit_cclip_round(std::vector<at::Tensor> xs,
                                            int64_t mode, int64_t iters,
                                            double tau, int64_t bucket,
                                            const at::Tensor& perm);
+std::vector<at::Tensor> fedkit_bulyan_round(std::vector<at::Tensor> xs,
+                                            const at::Tensor& z,
+                                            const at::Tensor& center,
+                                            double rho, int64_t mode,
+                                            int64_t f);
 
 std::vector<at::Tensor> fedkit_cross_entropy_fwd(const at::Tensor& logits,
                                                  const at::Tensor& labels);
@@ -260,6 +265,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "as aggregate_round's",
         py::arg("xs"), py::arg("z"), py::arg("rho"), py::arg("mode"),
         py::arg("iters"), py::arg("tau"), py::arg("bucket"), py::arg("perm"));
+  m.def("bulyan_round", &fedkit_bulyan_round,
+        "Bulyan round over K <= 32 clients, K >= 4 f + 3 (mode 0 fedavg, 1 "
+        "fedprox): K - 2 f clients picked by iterated Krum on the MFMA Gram "
+        "distances around `center`, then per element the mean of the K - 4 f "
+        "picked values closest to their median; returns (znew, res, sel int32 "
+        "[K], D, order int32 [K]) with res as aggregate_round's",
+        py::arg("xs"), py::arg("z"), py::arg("center"), py::arg("rho"),
+        py::arg("mode"), py::arg("f"));
   m.def("cross_entropy_fwd", &fedkit_cross_entropy_fwd,
         "fused log-softmax + NLL (mean): returns (loss, lse)");
   m.def("cross_entropy_bwd", &fedkit_cross_entropy_bwd, "CE backward");

@@ -69,7 +69,9 @@ class Strategy:
     # the clients and drop none; "cclip" is centred clipping: cclip_iters
     # clip steps of radius cclip_tau (0 = the median norm) around the old z,
     # over the means of random groups of agg_bucket clients (1 = the clients
-    # themselves); None is the mean.
+    # themselves); "bulyan" selects K - 2 f clients by iterated Krum and
+    # averages, per coordinate, the K - 4 f selected values closest to their
+    # median, f = floor(trim_frac * K), K >= 4 f + 3; None is the mean.
     robust: Optional[str] = None
     trim_frac: float = 0.1
     geomed_iters: int = 16
@@ -108,7 +110,8 @@ class Strategy:
         that defines it when fused_aggregate is off; same z either way.  The
         Krum rules leave their selection in state["krum_selected"], the
         geometric median its weights in state["geomed_weights"], centred
-        clipping its weights in state["cclip_weights"]."""
+        clipping its weights in state["cclip_weights"], Bulyan its selection
+        in state["bulyan_selected"]."""
         fused = (self.fused_aggregate
                  and comm.K <= consensus.MAX_FUSED_CLIENTS)
         if self.robust == "cclip":
@@ -124,6 +127,16 @@ class Strategy:
                   else consensus.geomed_round_torch)
             znew, res, state["geomed_weights"] = fn(
                 pending(), state["z"], rho, mode, self.geomed_iters)
+            return znew, res
+        if self.robust == "bulyan":
+            f = consensus.bulyan_params(self.trim_frac, comm.K)[0]
+            if fused:
+                znew, res, sel = consensus.bulyan_round(
+                    pending(), state["z"], rho, mode, f, center=state["z"])
+            else:
+                znew, res, sel = consensus.bulyan_round_torch(
+                    pending(), state["z"], rho, mode, f)
+            state["bulyan_selected"] = sel
             return znew, res
         if self.robust in consensus.KRUM_RULES:
             f, m = consensus.krum_params(self.robust, self.trim_frac, comm.K)

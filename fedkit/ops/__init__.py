@@ -31,6 +31,10 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
                                  clients: the same Gram pass, the bucket
                                  contraction and the clip iterations on the
                                  device, the same weighted pass (FedAvg/FedProx)
+  bulyan_round                   Bulyan round over K clients: the same Gram
+                                 pass, iterated Krum in one workgroup, then a
+                                 sorting-network pass that averages the values
+                                 closest to the median (FedAvg/FedProx)
 
 Dispatch policy (this is the "native code is THE path that runs" rule):
   * on a ROCm GPU the HIP kernels are used; if the extension is missing the

@@ -27,6 +27,9 @@ the device, and one weighted pass (csrc/geomed.hip).  `cclip_round` is
 centred clipping with bucketing: the clients are averaged in random groups,
 the group means are clipped towards the old consensus, again iterated on the
 Gram matrix on the device, and the same weighted pass (csrc/cclip.hip).
+`bulyan_round` composes the two families: iterated Krum on the Gram distances
+selects the clients on the device, and a sorting-network pass averages, per
+coordinate, the selected values closest to their median (csrc/bulyan.hip).
 
 All vectors are fp32 in PHYSICAL (storage) element order, the order
 flat.pack / paramvec.flat_physical use.  Dispatch follows the package rule:
@@ -209,7 +212,8 @@ def aggregate_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
 
 
 KRUM_RULES = ("krum", "multi_krum")
-ROBUST_RULES = ("trimmed_mean", "median") + KRUM_RULES + ("geomed", "cclip")
+ROBUST_RULES = ("trimmed_mean", "median") + KRUM_RULES + ("geomed", "cclip",
+                                                          "bulyan")
 
 
 def robust_trim(rule: str, trim_frac: float, K: int) -> int:
@@ -631,6 +635,133 @@ def cclip_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
             perm.to(z.device))
         return znew, res, w
     return cclip_round_torch(xs, z, rho, mode, iters, tau, bucket, perm)
+
+
+def bulyan_params(trim_frac: float, K: int):
+    """(f, theta, beta) of a Bulyan round: f = floor(trim_frac * K) clients
+    may be bad, theta = K - 2 f are selected and beta = K - 4 f values are
+    averaged per coordinate.  Needs K >= 4 f + 3."""
+    f = math.floor(trim_frac * K)
+    _check_bulyan(K, f, "fedavg")
+    return f, K - 2 * f, K - 4 * f
+
+
+def _check_bulyan(K: int, f: int, mode: str):
+    if mode == "admm":
+        raise ValueError("there is no robust ADMM round; use fedavg or fedprox")
+    assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+    if f < 0 or K < 4 * f + 3:
+        raise ValueError(f"Bulyan needs f >= 0 and K >= 4 f + 3, got f = {f} "
+                         f"of K = {K}")
+
+
+def bulyan_window_torch(xs: Sequence[torch.Tensor], sel: torch.Tensor,
+                        f: int) -> torch.Tensor:
+    """Steps 3 and 4 of `bulyan_round` over the clients of the bool mask
+    `sel`: znew, bit for bit."""
+    picked = sel.nonzero().flatten().tolist()
+    theta, beta = len(picked), len(picked) - 2 * f
+    s = torch.sort(torch.stack([xs[k] for k in picked]), dim=0).values
+    mid = (theta - 1) // 2
+    med = s[mid]
+    first = max(0, mid - beta + 1)
+    lo = torch.full(med.shape, first, dtype=torch.long, device=med.device)
+    go = torch.ones_like(lo, dtype=torch.bool)
+    for c in range(first, min(mid, theta - beta)):
+        go &= (s[c + beta] - med) < (med - s[c])
+        lo += go
+    znew = torch.zeros_like(med)
+    for r in range(beta):
+        znew += s.gather(0, (lo + r)[None])[0]
+    znew /= beta
+    return znew
+
+
+def bulyan_round_torch(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                       rho: Optional[float] = None, mode: str = "fedavg",
+                       f: int = 0):
+    """The torch sequence that defines `bulyan_round` (the rule is stated
+    there), on the operands' device and in their dtype, directly on the
+    vectors; returns (znew, res, sel).  It reads each pick on the host."""
+    xs = list(xs)
+    K = len(xs)
+    _check_bulyan(K, f, mode)
+    D = _pairwise_sqdist_torch(xs)
+    inf = torch.full_like(D, math.inf)
+    D.fill_diagonal_(math.inf)          # D_ii is excluded
+    sel = torch.zeros(K, dtype=torch.bool, device=z.device)
+    for t in range(K - 2 * f):
+        q = max(1, K - t - f - 2)
+        near = torch.sort(torch.where(sel[None, :], inf, D), dim=1,
+                          stable=True).values
+        score = torch.zeros_like(near[:, 0])
+        if K - t > 1:                   # a lone remaining client scores 0
+            for r in range(q):          # ascending order
+                score += near[:, r]
+        left = (~sel).nonzero().flatten()
+        sel[left[torch.argsort(score[left], stable=True)[0]]] = True
+    znew = bulyan_window_torch(xs, sel, f)
+    res = [torch.norm(z - znew) ** 2]
+    if mode != "fedavg":
+        res += [torch.norm(rho * (x - znew)) ** 2 for x in xs]
+    return znew, torch.stack(res), sel
+
+
+def bulyan_round(xs: Sequence[torch.Tensor], z: torch.Tensor,
+                 rho: Optional[float] = None, mode: str = "fedavg", f: int = 0,
+                 center: Optional[torch.Tensor] = None):
+    """One Bulyan aggregation round (El Mhamdi, Guerraoui and Rouault, 2018)
+    over the K client vectors `xs`, of which up to `f` may be Byzantine,
+    K >= 4 f + 3.  Krum accepts a client that is close to the others in norm
+    but wrong in a few coordinates; the coordinate-wise rules accept one whose
+    every coordinate is in range while the vector is not.  Bulyan runs both:
+    theta = K - 2 f clients are selected by iterated Krum and, per
+    coordinate, the beta = K - 4 f selected values closest to their median
+    are averaged.  f = 0 is the plain mean.  The rule:
+
+      1. D is `pairwise_sqdist`: a non-finite entry counts as +inf, the
+         diagonal is zero, the matrix is exactly symmetric.
+      2. R = all K clients; theta times: q = max(1, |R| - f - 2) (the clamp
+         serves the last iterations, where |R| < f + 3), score_i for i in R
+         is the sum of the q smallest D_ij over the other j in R, added in
+         ascending order (a lone remaining client scores 0), and the client
+         of lowest score, ties to the lower index, moves from R to S.  With
+         q = 1 two mutually nearest clients share one D entry and tie
+         exactly; D's symmetry makes the index decide alike on every path.
+      3. Per coordinate, s = the theta values of S in torch.sort's order
+         (-inf < finite < +inf < NaN), mid = (theta - 1) // 2, med = s[mid],
+         lo = max(0, mid - beta + 1), go = True, and for
+         c = lo ... min(mid, theta - beta) - 1:
+         go &= (s[c + beta] - med) < (med - s[c]); lo += go.  The window
+         s[lo .. lo + beta - 1] always holds the median and, away from ties,
+         is the beta values closest to it; a NaN compares false and never
+         enters by sliding.  At most 2 f steps.
+      4. znew = zeros; znew += s[lo + r] for r = 0 .. beta - 1; znew /= beta.
+
+    Returns (znew, res, sel): znew and res as `robust_round` (res[1 + k] for
+    all K clients in fedprox mode, NaN for a NaN client), sel the bool [K]
+    mask of S on z's device, formed without a host sync.  Modes are fedavg
+    and fedprox.  On the GPU (csrc/bulyan.hip, K <= 32) the distances come
+    from the MFMA Gram pass around `center` (None means z), the selection
+    runs in one workgroup and the window in a sorting-network pass; znew is
+    bitwise steps 3 and 4 of `bulyan_round_torch`, the CPU path, over the
+    same selection.
+    """
+    xs = list(xs)
+    if mode != "fedavg" and mode != "admm":
+        assert rho is not None, f"{mode} needs rho"
+    if _use_native(z):
+        if mode == "admm":
+            raise ValueError("there is no robust ADMM round; use fedavg or "
+                             "fedprox")
+        assert mode in AGGREGATE_MODES, f"unknown mode {mode!r}"
+        from . import require_ext
+        znew, res, sel, _, _ = require_ext().bulyan_round(
+            xs, z, z if center is None else center,
+            0.0 if rho is None else float(rho), AGGREGATE_MODES.index(mode),
+            int(f))
+        return znew, res, sel.bool()
+    return bulyan_round_torch(xs, z, rho, mode, f)
 
 
 def bb_stats(y: torch.Tensor, yhat0: torch.Tensor, x: torch.Tensor,

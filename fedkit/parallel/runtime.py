@@ -114,12 +114,15 @@ class FedConfig:
                                        # coordinate-wise rules) | krum |
                                        # multi_krum (distance-based) | geomed
                                        # (geometric median, RFA) | cclip
-                                       # (centred clipping) of a FedAvg /
+                                       # (centred clipping) | bulyan
+                                       # (iterated Krum, then a median window
+                                       # per coordinate) of a FedAvg /
                                        # FedProx round (none = mean)
     trim_frac: float = 0.1             # trimmed_mean drops floor(trim_frac*K)
                                        # client values at each end; the Krum
-                                       # rules take f = floor(trim_frac*K)
-                                       # as the number of bad clients
+                                       # rules and bulyan take f =
+                                       # floor(trim_frac*K) as the number of
+                                       # bad clients
     geomed_iters: int = 16             # geomed: smoothed Weiszfeld steps
     cclip_iters: int = 3               # cclip: clip steps around the old z
     cclip_tau: float = 0.0             # cclip: clip radius; 0 = the median

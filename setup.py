@@ -23,6 +23,7 @@ SOURCES = [
     "csrc/krum.hip",
     "csrc/geomed.hip",
     "csrc/cclip.hip",
+    "csrc/bulyan.hip",
     "csrc/loss.hip",
     "csrc/losses_extra.hip",
     "csrc/linear.hip",

@@ -61,6 +61,12 @@ consensus.cclip_round (csrc/cclip.hip) against cclip_round_torch on the GPU
 geomed_round at the same K, N and iters.  One further row per K times
 iters = 3 against iters = 1024.
 
+Section `bulyan`: one Bulyan round at K = 10, f = 1 (fedavg / fedprox) and
+K = 32, f = 7 (fedavg), N of the ResNet18 last conv block:
+consensus.bulyan_round (csrc/bulyan.hip) against bulyan_round_torch on the GPU
+(wall: it reads every pick on the host), and a device-time row against
+krum_round (Multi-Krum, the same f).
+
 Method: warm-up, then SAMPLES samples per path taken alternately (fused,
 torch, fused, ...), each sample ITERS back-to-back calls between two device
 events; the reported figure is the median sample in microseconds per call.
@@ -402,12 +408,38 @@ def cclip_section(dev, row):
                                                  0.0, 2, perm)))
 
 
+def bulyan_section(dev, row):
+    name, n = "ResNet18 last conv block", AGG_SIZES["ResNet18 last conv block"]
+    for K, f, modes in ((10, 1, ("fedavg", "fedprox")), (32, 7, ("fedavg",))):
+        g = torch.Generator().manual_seed(8)
+        z = (torch.randn(n, generator=g) * 0.05).to(dev)
+        xs = [z + (torch.randn(n, generator=g) * 0.01).to(dev)
+              for _ in range(K)]
+        for mode in modes:
+            def fused():
+                return consensus.bulyan_round(xs, z, RHO, mode, f)
+
+            def sequence():
+                return consensus.bulyan_round_torch(xs, z, RHO, mode, f)
+
+            (za, _, sa), (zb, _, sb) = fused(), sequence()
+            print(f"{name} bulyan {mode} K={K}: selection equal "
+                  f"{torch.equal(sa, sb)}, znew equal {torch.equal(za, zb)}",
+                  flush=True)
+            row(f"{name}: bulyan {mode} K={K} f={f} (wall)", n,
+                ab(fused, sequence, sampler=sample_wall_us))
+            row(f"{name}: bulyan {mode} vs multi_krum f={f} K={K} "
+                "(device; columns: bulyan, krum, krum/bulyan)", n,
+                ab(fused, lambda: consensus.krum_round(xs, z, RHO, mode, f)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table here")
     ap.add_argument("--section", default="all",
                     choices=["all", "penalty", "aggregate", "bb",
-                             "robust", "krum", "geomed", "cclip"])
+                             "robust", "krum", "geomed", "cclip",
+                             "bulyan"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_penalty needs a GPU")
@@ -499,6 +531,8 @@ def main():
         geomed_section(dev, row)
     if args.section in ("all", "cclip"):
         cclip_section(dev, row)
+    if args.section in ("all", "bulyan"):
+        bulyan_section(dev, row)
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
