@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "conv_plan.h"
+#include "infonce_plan.h"
 #include "linear_plan.h"
 
 at::Tensor fedkit_elu_fwd(const at::Tensor& x);
@@ -177,6 +178,11 @@ std::vector<at::Tensor> fedkit_info_nce_bwd(const at::Tensor& Z,
                                             const at::Tensor& dzz,
                                             const at::Tensor& tu,
                                             const at::Tensor& norms);
+std::vector<at::Tensor> fedkit_info_nce_tiled_fwd(const at::Tensor& Z,
+                                                  const at::Tensor& Zhat);
+std::vector<at::Tensor> fedkit_info_nce_tiled_bwd(
+    const at::Tensor& Z, const at::Tensor& Zhat, const at::Tensor& zz,
+    const at::Tensor& soft, const at::Tensor& norms, const at::Tensor& gloss);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "fedkit hand-written CDNA4 (gfx950 / MI355X) kernels";
@@ -398,4 +404,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("info_nce_fwd", &fedkit_info_nce_fwd,
         "fused InfoNCE: returns (loss, zz, softmax, norms)");
   m.def("info_nce_bwd", &fedkit_info_nce_bwd, "InfoNCE backward");
+  m.def("info_nce_tiled_fwd", &fedkit_info_nce_tiled_fwd,
+        "tiled fp32-MFMA InfoNCE, 64 < P <= 1024: (loss, zz, softmax, norms)");
+  m.def("info_nce_tiled_bwd", &fedkit_info_nce_tiled_bwd,
+        "tiled InfoNCE backward (Z, Zhat, zz, soft, norms, gloss) -> "
+        "(gZ, gZhat)");
+  m.def("info_nce_tiled_plan",
+        [](long D, long P) {
+          auto p = fedkit_plan::plan_info_nce(D, P);
+          return py::make_tuple(p.tiles_p * p.tiles_p, p.splits);
+        },
+        "similarity-pass plan of the tiled InfoNCE: (tiles, splits of D)");
 }

@@ -9,6 +9,9 @@ in-tree, gfx950-only) provides the hand-written MI355X kernels:
   conv2d_fwd / conv2d_bwd_*      NHWC implicit-GEMM conv on MFMA (3x3, 1x1)
   bn_fwd / bn_bwd                NHWC BatchNorm with fused ELU epilogue
   cross_entropy_fwd/bwd          fused log-softmax + NLL
+  info_nce_fwd/bwd               one-workgroup InfoNCE, patch grids P <= 64
+  info_nce_tiled_fwd/bwd         InfoNCE for 64 < P <= 1024: tiled fp32 MFMA
+                                 similarity and gradient GEMMs, split D
   add_elu_fwd / add_elu_bwd      fused residual-add + ELU
   penalty_fwd / penalty_bwd      fused FedProx/ADMM penalty + L1/L2 regulariser
   admm_dual_update / bb_stats    fused ADMM y-update and BB inner products

@@ -227,6 +227,31 @@ class _InfoNceFn(torch.autograd.Function):
         return gZ, gZhat
 
 
+class _InfoNceTiledFn(torch.autograd.Function):
+    """InfoNCE for 64 < px*py <= 1024 (csrc/infonce_tiled.hip): the similarity
+    matrix and both gradient products as tiled fp32 MFMA GEMMs; the column
+    norms come out of the similarity pass, dzz / t / u are formed on the
+    device from gloss's device pointer."""
+
+    @staticmethod
+    def forward(ctx, Z, Zhat):
+        from . import require_ext
+        loss, zz, soft, norms = require_ext().info_nce_tiled_fwd(Z, Zhat)
+        ctx.save_for_backward(Z, Zhat, zz, soft, norms)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        from . import require_ext
+        gZ, gZhat = require_ext().info_nce_tiled_bwd(*ctx.saved_tensors,
+                                                     gloss)
+        return gZ, gZhat
+
+
+_NCE_ONE_WG_MAX_P = 64      # kMaxP of csrc/losses_extra.hip
+_NCE_TILED_MAX_P = 1024     # kNceMaxP of csrc/infonce_plan.h
+
+
 def info_nce(z: torch.Tensor, zhat: torch.Tensor) -> torch.Tensor:
     """InfoNCE over the patch grid (federated_cpc.py:149-180).
 
@@ -234,14 +259,20 @@ def info_nce(z: torch.Tensor, zhat: torch.Tensor) -> torch.Tensor:
     diagonal of the (px*py)^2 normalized inner-product matrix; negatives are
     the rest of its row.  GPU: one fused kernel; CPU: one GEMM + row softmax
     (both replace the reference's O(p^4) Python loop, identical values).
+
+    GPU dispatch on P = px*py: P <= 64 the one-workgroup kernel, 64 < P <=
+    1024 the tiled fp32-MFMA kernels (fp32 or bf16 inputs, fp32 loss), above
+    1024 the torch sequence below.
     """
     assert z.shape == zhat.shape
     px, py = z.shape[2], z.shape[3]
     P = px * py
     Z = z.reshape(-1, P)
     Zhat = zhat.reshape(-1, P)
-    if _native(z) and P <= 64:
+    if _native(z) and P <= _NCE_ONE_WG_MAX_P:
         return _InfoNceFn.apply(Z.contiguous(), Zhat.contiguous())
+    if _native(z) and P <= _NCE_TILED_MAX_P:
+        return _InfoNceTiledFn.apply(Z.contiguous(), Zhat.contiguous())
     Zn = Z / Z.norm(dim=0, keepdim=True)
     Zhatn = Zhat / Zhat.norm(dim=0, keepdim=True)
     zz = Zn.t() @ Zhatn                     # [P, P]

@@ -26,6 +26,7 @@ SOURCES = [
     "csrc/bulyan.hip",
     "csrc/loss.hip",
     "csrc/losses_extra.hip",
+    "csrc/infonce_tiled.hip",
     "csrc/linear.hip",
     "csrc/linear_mfma.hip",
     "csrc/adam.hip",
